@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py — training images/sec of the contrast_train hot path at B=16 x 448 x 448 per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (images/sec, ms_per_step).  --full adds the
+rest of the evidence: the conv roofline (HIP events inside the timed steps), the parity-mode throughputs, the similarity
+kernels against the HBM roof, the inference geometry and the CPU-oracle baseline.  --dump-outputs DIR writes what the last
+timed step handed its caller (loss scalars, a fixed sample of the updated weights and their gradients) as DIR/<name>.npy.
 
 N>1: one process per GPU over RCCL.  Either the caller launches the ranks (`python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ...`: RANK / WORLD_SIZE are in the environment) or — when RANK is unset — this process starts that launcher
@@ -155,6 +160,27 @@ def infer_section(dev, n_img=8):
             "frac_of_bf16_peak": round(flops / dt / 1e12 / PEAK_BF16_TFLOPS, 4), "val_set_1449_images_sec": round(1449 * dt, 1)}
 
 
+DUMP_SAMPLE = 1 << 20       # elements of the weight / gradient samples: 4 MB each in float32
+DUMP_SAMPLE_SEED = 20250    # fixed, independent of --seed: every run samples the same elements
+
+
+def dump_outputs(out_dir, model, losses):
+    """What a caller of Trainer.step holds after the last timed step, as <out_dir>/<name>.npy in float32: the logged loss scalars,
+    and the same seeded sample of the trainable weights (after the optimizer step) and of their gradients, over the parameters'
+    logical layout in named_parameters order (independent of how the engine packs them)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in losses.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v.detach().float().cpu().numpy())
+    params = [p for _, p in model.named_parameters() if p.requires_grad]
+    w = torch.cat([p.detach().reshape(-1) for p in params]).float()
+    g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params]).float()
+    gen = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+    idx = torch.randint(0, w.numel(), (min(DUMP_SAMPLE, w.numel()),), generator=gen).sort()[0].to(w.device)
+    np.save(os.path.join(out_dir, "weights_sample.npy"), w[idx].cpu().numpy())
+    np.save(os.path.join(out_dir, "grads_sample.npy"), g[idx].cpu().numpy())
+
+
 def _spawn_ranks(a):
     """--gpus N without a launcher: start `torch.distributed.run` as a child process (this process has made no GPU call)."""
     with socket.socket() as s_:
@@ -209,14 +235,18 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--size", type=int, default=448)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "bf16x3"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the `similarity` (HBM roof of the pixel-to-prototype kernels) and `infer_mode` (config 5 geometry) sections")
-    ap.add_argument("--cpu-baseline-n", default="2,16", help="batch sizes of the CPU-oracle leg (BASELINE.md §3: N=2 and N=16)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, parity modes, similarity / inference sections and the CPU baseline (options below marked --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss scalars, fixed samples of the updated weights and gradients) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU-oracle leg")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the `similarity` (HBM roof of the pixel-to-prototype kernels) and `infer_mode` (config 5 geometry) sections")
+    ap.add_argument("--cpu-baseline-n", default="2,16", help="--full: batch sizes of the CPU-oracle leg (BASELINE.md §3: N=2 and N=16)")
     ap.add_argument("--parity-steps", type=int, default=2,
-                    help="timed steps of the parity (f32-exact) mode reported as `parity_mode` beside the bf16 line (0: skip)")
+                    help="--full: timed steps of the parity (f32-exact) mode reported as `parity_mode` beside the bf16 line (0: skip)")
     ap.add_argument("--parity-precision", default=os.environ.get("WSEG_PARITY_PRECISION", "fp32,bf16x3"),
-                    help="comma list of the parity-grade modes to time: fp32 (exact-f32 MFMA), bf16x3 (f32 storage, split-bf16 products)")
-    ap.add_argument("--event-stride", type=int, default=5, help="bracket every k-th conv launch with HIP events (rotating)")
+                    help="--full: comma list of the parity-grade modes to time: fp32 (exact-f32 MFMA), bf16x3 (f32 storage, split-bf16 products)")
+    ap.add_argument("--event-stride", type=int, default=5, help="--full: bracket every k-th conv launch with HIP events (rotating)")
     ap.add_argument("--no-lookahead", action="store_true", help="do not tell step i the images of step i + 1 (A/B switch: the frozen prefix of the "
                                                                 "next forward pass then runs in front of it instead of inside the loss phase)")
     ap.add_argument("--seed", type=int, default=0, help="base seed: rank r draws its images / labels / dropout masks / keys from seed + r")
@@ -224,6 +254,8 @@ def main():
                     help="base lr; the reference's 0.01 makes the RANDOM procedural weights diverge within 2 steps "
                          "(measured, scripts/debug_step.py), so the bench steps with a small lr — same kernels, same work")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "RANK" not in os.environ:              # no launcher above us: be the launcher (child process, no exec)
         sys.exit(_spawn_ranks(a))
@@ -289,19 +321,23 @@ def main():
 
     for i in range(a.warmup):
         one_step(i)
-    # HIP events around the conv_igemm launches, live in the timed region, on the launch stream.  An event pair costs
+    # --full: HIP events around the conv_igemm launches, live in the timed region, on the launch stream.  An event pair costs
     # ~10 us of stream time, so launch i of step s is bracketed only when (i + s) % stride == 0: every launch index
     # is sampled steps/stride times while the timed region slows by ~0.2 ms/step instead of ~1 ms.
-    L.PROFILE = []
-    L.PROFILE_STRIDE = max(1, min(a.event_stride, a.steps))
+    if a.full:
+        L.PROFILE = []
+        L.PROFILE_STRIDE = max(1, min(a.event_stride, a.steps))
     barrier()
     t0 = time.perf_counter()
     for it in range(a.steps):
-        L.profile_begin_step(it)
+        if a.full:
+            L.profile_begin_step(it)
         losses = one_step(a.warmup + it)
     barrier()
     dt = time.perf_counter() - t0
     prof, L.PROFILE = L.PROFILE, None
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, model, losses)
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -310,7 +346,7 @@ def main():
     value = a.batch * world * a.steps / dt
     PEAKS = {"bf16": PEAK_BF16_TFLOPS, "fp32": PEAK_F32_TFLOPS, "bf16x3": PEAK_BF16_TFLOPS / 3}
 
-    if rank == 0:
+    if rank == 0 and a.full:
         # dominant kernel: the implicit-GEMM conv (fwd + dgrad launches), timed with HIP events on the
         # launch stream during the timed region
         per_idx = {}                                           # launch index within a step -> [sum ms, samples, flops]
@@ -338,6 +374,7 @@ def main():
                 "launches_per_step": n_launch // a.steps, "event_samples": len(prof),
                 "avg_launch_ms": round(tot_ms / n_launch, 4), "avg_launch_gflop": round(tot_fl / n_launch / 1e9, 2),
                 "whole_step_frac": round(conv_flops_model() * a.batch / (ms * 1e-3) / 1e12 / peak, 4)}
+    if rank == 0:
         line = {"metric": "training images/sec at B=16x448x448 (contrast_train step)", "value": round(value, 2),
                 "unit": "images/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
                 "ms_per_step": round(ms, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -346,9 +383,11 @@ def main():
                                        f"procedural weights, dropout on, fused HIP loss",
                            "global_batch": a.batch * world, "parallelism": f"dp{world}", "seed": a.seed,
                            "input": "two synthetic batches alternate" + ("; step i is given the images of step i+1 (prefetching-loader lookahead)" if look else "")},
-                "loss": float(losses["loss"]), "roofline": roof}
+                "loss": float(losses["loss"])}
+        if a.full:
+            line["roofline"] = roof
     # ---- the parity mode's throughput (the mode the 1e-4 / argmax-exact evidence is for), same workload, rank 0 at N=1 only
-    if rank == 0 and world == 1 and a.parity_steps > 0 and a.precision == "bf16":
+    if a.full and rank == 0 and world == 1 and a.parity_steps > 0 and a.precision == "bf16":
         del trainer, model
         torch.cuda.empty_cache()
         line["parity_mode"] = []
@@ -365,11 +404,11 @@ def main():
             torch.cuda.empty_cache()
     # ---- the rest of the north star's evidence, rank 0 at N=1 only, after the training measurement: the similarity kernels against the HBM
     #      roof and BASELINE config 5's inference geometry
-    if rank == 0 and world == 1 and not a.no_extras:
+    if a.full and rank == 0 and world == 1 and not a.no_extras:
         line["similarity"] = similarity_section(dev)
         line["infer_mode"] = infer_section(dev)
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(tuple(int(x) for x in a.cpu_baseline_n.split(",")))
         print(json.dumps(line), flush=True)
     if dist.is_initialized():

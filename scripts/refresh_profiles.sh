@@ -19,5 +19,5 @@ cd "$ROOT" &&
 timeout -k 10 300 python scripts/profile_layers.py bf16 > "$OUT/${R}_layers_b16_448_bf16.txt" 2>&1 && echo "layers ok" &&
 timeout -k 10 300 python scripts/bench_nce_sweep.py > "$OUT/${R}_nce_similarity_sweep.txt" 2>&1 && echo "sweep ok" &&
 (for p in bf16 bf16x3 fp32; do timeout -k 10 200 python scripts/bench_infer.py $p 16; done) > "$OUT/${R}_infer_375x500.txt" 2>&1 && echo "infer ok" &&
-timeout -k 10 900 python bench.py --steps 20 --warmup 5 > "$OUT/${R}_bench_b16_448_bf16.json" 2> "$OUT/bench.err"
+timeout -k 10 900 python bench.py --full --steps 20 --warmup 5 > "$OUT/${R}_bench_b16_448_bf16.json" 2> "$OUT/bench.err"
 echo "bench rc=$?"; tail -c 2500 "$OUT/${R}_bench_b16_448_bf16.json"; cat "$OUT/${R}_infer_375x500.txt" | grep inference
