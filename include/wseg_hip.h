@@ -55,6 +55,8 @@ const char* wseg_last_error(void);
  *                  out2 = relu(v*scale[c]+shift[c]) * drop[n,c]          (when out2 != NULL)
  *     epi 1      : out  = v*scale[c]*drop[n,c]*(mask>0) + r_post          (BN-ReLU backward)
  *     epi 2      : out  = relu(v)                                         (f8_3/f8_4/fc_proj)
+ *     epi 3      : out  = elu(v) = v > 0 ? v : expm1(v)                   (the AffinityNet head f8_3/f8_4/f8_5/f9,
+ *                                                                          network/resnet38_aff.py:44-47; 64 / 128-row tiles)
  *   NULL scale/shift/drop/mask/r_post mean 1/0/1/all-pass/0.
  */
 typedef struct wseg_conv_desc {
@@ -326,6 +328,39 @@ int wseg_augment_batch(const wseg_aug_desc* descs_dev, int n, int max_pixels /* 
 int wseg_sgd_step(float* params, const float* grads, float* momentum_buf, long numel,
                   const long* seg_begin, const long* seg_end, const float* seg_lr, const float* seg_wd, int nseg,
                   float momentum, float grad_scale, int first_step, void* bf16_mirror, void* stream);
+
+/* ---- AffinityNet inference: random-walk CAM refinement (network/resnet38_aff.py, aff_infer.py:14-141) -------------------
+ * Pair set of radius r (tool/pyutils.py get_indices_of_pairs) on an h x w feature map, pixel p = y*w + x:
+ *   offsets (dy, dx), in this order: (0, 1..r-1), then for dy = 1..r-1 every dx in (-r, r) with dx*dx + dy*dy < r*r;  P = their count
+ *   (r = 5: 34).  "from" pixels: rows [0, h-r+1) x columns [r-1, w-r+1) (the reference's crop, asymmetric: the first r-1 columns
+ *   have no edge to the right), n_from = (h-r+1) * (w-2r+2), f = row-major index inside that rectangle; "to" = from + (dy, dx).
+ *   2 <= r <= 6 (r = 1 has no offsets: the reference fails there).  Callers pick r = (min(h,w)-1)/2 below 11, else 5.
+ * The affinity matrix A (area = h*w) is symmetric: A[from][to] = A[to][from] = aff, A[i][i] = 1, every other entry 0. */
+#define WSEG_AFF_MAX_OFFSETS 64
+#define WSEG_RW_MAX_PLANE 8192      /* largest h*w wseg_random_walk accepts (two f32 planes in 64 KiB of LDS); larger maps are refused */
+int wseg_aff_num_offsets(int radius);      /* P, or -1 for a radius outside [2, 6] */
+/* aff[n][p][f] = exp(-mean_c |feat[to] - feat[from]|) over C channels, f32 accumulation (network/resnet38_aff.py:68-72).
+ * feat: pixel rows [N*h*w][ld] in `dtype` (f32 or bf16; C % 8 == 0, ld % 8 == 0, C <= 512). */
+int wseg_aff_pairs(const void* feat, int ld, int C, float* aff, int N, int h, int w, int radius, int dtype, void* stream);
+/* the dense [area][area] f32 A of ONE image (network/resnet38_aff.py:74-89, forward(x, to_dense=True)): zeroes `dense`, then
+ * scatters both orientations of every pair and the unit diagonal. */
+int wseg_aff_to_dense(const float* aff, float* dense, int h, int w, int radius, void* stream);
+/* random-walk stencil of N images (aff_infer.py:100-102): wgt[n][q][j] = A^beta[i][j] for the neighbour i of column j in slot q
+ * (q < P: i = j + offset q, j a "from" pixel; P <= q < 2P: i = j - offset (q-P), i a "from" pixel; 0 where no such edge), and
+ * rsum[n][j] = 1 / sum_i A^beta[i][j] (the diagonal counts: every sum is >= 1).  wgt: [N][2P][h*w], rsum: [N][h*w]. */
+int wseg_rw_prepare(const float* aff, float* wgt, float* rsum, int N, int h, int w, int radius, int beta, void* stream);
+/* 2^logt steps of v[j] <- (v[j] + sum_q v[i_q] wgt[q][j]) * rsum[j] on every plane: v_out = v_in . T^(2^logt) with T = A^beta / colsum
+ * (aff_infer.py:103-108 computes the same product by logt dense squarings).  v_in / v_out: [N][planes][h*w] f32 (may alias).
+ * One workgroup per plane, the plane ping-ponged in LDS; h*w <= WSEG_RW_MAX_PLANE. */
+int wseg_random_walk(const float* wgt, const float* rsum, const float* v_in, float* v_out, int N, int planes, int h, int w, int radius,
+                     int logt, void* stream);
+/* the walk's input of one image (aff_infer.py:85-98): a 21-plane [21][H][W] map with plane 0 = bg, plane c = cams[src[c]] for
+ * src[c] >= 0 (zero when src[c] < 0), zero padded to [8*dh][8*dw], then 8x8 average pooling -> pooled [21][dh][dw].
+ * cams: [ncams][H][W] f32 device; src: 21 host ints. */
+int wseg_rw_pool(const float* cams, const int* src, float bg, float* pooled, int H, int W, int dh, int dw, void* stream);
+/* bilinear upsample (align_corners=False) of cam_rw [planes][dh][dw] to [8*dh][8*dw], arg-max over the planes (the first maximum wins),
+ * cropped to [H][W] (aff_infer.py:110-139): pred uint8 [H][W].  planes <= 32. */
+int wseg_rw_finish(const float* cam_rw, unsigned char* pred, int planes, int dh, int dw, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

@@ -387,3 +387,19 @@ def split_bf16(inp, hi, lo): _call("wseg_split_bf16", _v(inp), _v(hi), _v(lo), C
 def pack_x3(src, dst): _call("wseg_pack_x3", _v(src), _v(dst), C.c_long(src.numel()))
 def pcm_forward_bf16(Fb, Gb, cam_rv, den, N, hw): _call("wseg_pcm_forward_bf16", _v(Fb), _v(Gb), _v(cam_rv), _v(den), N, hw)
 def pcm_backward_bf16(Fb, Gb, Gl, d_cam_rv, cam_rv, den, DN, DNb, DNl, dFh, N, hw): _call("wseg_pcm_backward_bf16", _v(Fb), _v(Gb), _v(Gl), _v(d_cam_rv), _v(cam_rv), _v(den), _v(DN), _v(DNb), _v(DNl), _v(dFh), N, hw)
+
+
+# ---------------------------------------------------------------------------------------------- AffinityNet inference (csrc/affinity.hip)
+RW_MAX_PLANE = 8192          # WSEG_RW_MAX_PLANE
+
+
+def aff_num_offsets(radius): return int(lib.wseg_aff_num_offsets(radius))
+def aff_pairs(feat, ld, C_, aff, N, h, w, radius): _call("wseg_aff_pairs", _v(feat), ld, C_, _v(aff), N, h, w, radius, dtype_code(feat))
+def aff_to_dense(aff, dense, h, w, radius): _call("wseg_aff_to_dense", _v(aff), _v(dense), h, w, radius)
+def rw_prepare(aff, wgt, rsum, N, h, w, radius, beta): _call("wseg_rw_prepare", _v(aff), _v(wgt), _v(rsum), N, h, w, radius, int(beta))
+def random_walk(wgt, rsum, v_in, v_out, N, planes, h, w, radius, logt):
+    _call("wseg_random_walk", _v(wgt), _v(rsum), _v(v_in), _v(v_out), N, planes, h, w, radius, int(logt))
+def rw_pool(cams, src, bg, pooled, H, W, dh, dw):
+    """src: 21 ints, plane c <- cams[src[c]] (-1: zero plane; plane 0 is the bg score)."""
+    _call("wseg_rw_pool", _v(cams), (C.c_int * 21)(*[int(s) for s in src]), _f(bg), _v(pooled), H, W, dh, dw)
+def rw_finish(cam_rw, pred, planes, dh, dw, H, W): _call("wseg_rw_finish", _v(cam_rw), _v(pred), planes, dh, dw, H, W)

@@ -39,6 +39,12 @@ HEAD_CONVS = OrderedDict([                       # resnet38_contrast.py:15-20
     ("f8_4",    (128, 1024)),
     ("f9",      (192, 195)),
 ])
+AFF_HEAD_CONVS = OrderedDict([                   # resnet38_aff.py:13-17 (AffinityNet: ELU branches on conv4 / conv5 / conv6, then f9)
+    ("f8_3", (64,  512)),
+    ("f8_4", (128, 1024)),
+    ("f8_5", (256, 4096)),
+    ("f9",   (448, 448)),
+])
 NUM_CLASSES = 21
 PROJ_DIM = 128
 BN_EPS = 1e-5
@@ -75,8 +81,9 @@ def block_bns(b):
             (f"{name}.bn_branch2b2", cout // 2)]
 
 
-def state_dict_spec():
-    """OrderedDict key -> shape, in the reference's state_dict() order (233 keys)."""
+def state_dict_spec(head_convs=None):
+    """OrderedDict key -> shape, in the reference's state_dict() order (233 keys with the contrast head).
+    head_convs: the net's head table (default HEAD_CONVS; AFF_HEAD_CONVS for the AffinityNet)."""
     spec = OrderedDict()
     spec["conv1a.weight"] = (64, 3, 3, 3)
 
@@ -104,7 +111,7 @@ def state_dict_spec():
             elif p in convs:
                 spec[p + ".weight"] = convs[p]
     add_bn("bn7", 4096)
-    for hname, (co, ci) in HEAD_CONVS.items():
+    for hname, (co, ci) in (HEAD_CONVS if head_convs is None else head_convs).items():
         spec[hname + ".weight"] = (co, ci, 1, 1)
     return spec
 
@@ -114,10 +121,11 @@ def _osz(h, k, s, d):
     return (h + 2 * p - d * (k - 1) - 1) // s + 1
 
 
-def forward_macs(H, W):
+def forward_macs(H, W, head_convs=None):
     """Algorithmic multiply-accumulates of ONE Net.forward on an H x W image (conv MACs = Cin * Cout * k^2 * h_out * w_out
     for every conv of resnet38d.py:160-189 and resnet38_contrast.py:34-54, PCM = hw^2 * (192 + 21), resnet38_contrast.py:70-73).
-    448 x 448 -> 403.697e9, 128 x 128 -> 32.798e9."""
+    448 x 448 -> 403.697e9, 128 x 128 -> 32.798e9.
+    head_convs: another head table (AFF_HEAD_CONVS): its 1x1 convs replace the contrast head and the PCM term."""
     macs = 3 * 64 * 9 * H * W                                   # conv1a, stride 1, same size
     h, w = H, W
     for b in BLOCKS:
@@ -128,6 +136,8 @@ def forward_macs(H, W):
             macs += ci * co * k * k * oh * ow                   # every conv of a block produces the block's output size
         h, w = oh, ow
     hw = h * w
+    if head_convs is not None:
+        return macs + hw * sum(co * ci for (co, ci) in head_convs.values())
     macs += hw * sum(co * ci for (co, ci) in HEAD_CONVS.values())
     macs += hw * hw * (192 + 21)
     return macs

@@ -129,6 +129,9 @@ __device__ __forceinline__ PermRow perm_decode(const Args& a, int m) {
 }
 
 
+// ELU with alpha = 1 (F.elu; the AffinityNet head, network/resnet38_aff.py:44-47)
+__device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : expm1f(x); }
+
 // Per-thread BN scale / shift of its 8-channel column group (1 / 0 when absent).
 __device__ __forceinline__ void epilogue_coeffs(const wseg_conv_desc& d, int n0, int cv, float (&sc)[8], float (&sh)[8]) {
   const int oc_raw = n0 + cv;
@@ -181,7 +184,7 @@ __device__ __forceinline__ void epilogue_image(const wseg_conv_desc& d, int M, c
 #pragma unroll
       for (int j = 0; j < CHK; ++j) load8<DT>(d.mask, mrow[j] * d.ld_mask + oc, mk[j]);
     }
-    if (EPI != 2 && has_drop) {
+    if (EPI < 2 && has_drop) {
 #pragma unroll
       for (int j = 0; j < CHK; ++j) load8<WSEG_F32>(d.drop, (size_t)wseg_decode_row(d, (int)mrow[j]).n_glob * d.OC + oc, dr[j]);
     }
@@ -232,9 +235,13 @@ __device__ __forceinline__ void epilogue_image(const wseg_conv_desc& d, int M, c
           o[e] = x;
         }
         if (ok[j]) store8<DT>(d.out, m * d.ld_out + oc, o);
-      } else {
+      } else if constexpr (EPI == 2) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+        if (ok[j]) store8<DT>(d.out, m * d.ld_out + oc, v);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = elu1(v[e]);
         if (ok[j]) store8<DT>(d.out, m * d.ld_out + oc, v);
       }
     }
@@ -282,7 +289,7 @@ __device__ __forceinline__ void wave_local_epilogue_batch(const Args& a, float* 
   const int vr = lane >> 3, vg = lane & 7;
   const bool ld_ok_ = WSEG_DIAG_EPI_LOADS();       // (probe builds only: compiled out of the product)
   const bool has_pre = d.r_pre != nullptr && ld_ok_, has_post = d.r_post != nullptr && ld_ok_, has_mask = EPI == 1 && d.mask != nullptr && ld_ok_;
-  const bool has_drop = EPI != 2 && d.drop != nullptr && ld_ok_;
+  const bool has_drop = EPI < 2 && d.drop != nullptr && ld_ok_;
   const bool res_is_pre = has_pre;                 // the prefetched residual: r_pre when present, else r_post
   const bool post_in_step = has_pre && has_post;
   const void* res_p = res_is_pre ? d.r_pre : d.r_post;
@@ -371,9 +378,13 @@ __device__ __forceinline__ void wave_local_epilogue_batch(const Args& a, float* 
           o[e] = x;
         }
         if (ok[i][t]) store8<DT>(d.out, m * d.ld_out + oc, o);
-      } else {
+      } else if constexpr (EPI == 2) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+        if (ok[i][t]) store8<DT>(d.out, m * d.ld_out + oc, v);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = elu1(v[e]);
         if (ok[i][t]) store8<DT>(d.out, m * d.ld_out + oc, v);
       }
     }
@@ -1122,7 +1133,7 @@ static int conv_validate(const wseg_conv_desc* d) {
   WSEG_CHECK(d->N > 0 && d->OH > 0 && d->OW > 0 && d->IH > 0 && d->IW > 0, "conv_igemm: empty shape");
   WSEG_CHECK(d->stride >= 1 && d->dil >= 1 && d->KH >= 1 && d->KW >= 1, "conv_igemm: bad geometry");
   WSEG_CHECK(d->mode == 0 || d->mode == 1, "conv_igemm: bad mode");
-  WSEG_CHECK(d->epi >= 0 && d->epi <= 2, "conv_igemm: bad epilogue");
+  WSEG_CHECK(d->epi >= 0 && d->epi <= 3, "conv_igemm: bad epilogue");
   WSEG_CHECK(d->ld_in >= d->IC, "conv_igemm: ld_in < IC");
   if (d->out) WSEG_CHECK(d->ld_out >= d->OC && d->ld_out % 8 == 0, "conv_igemm: bad ld_out");
   if (d->out2) WSEG_CHECK(d->ld_out2 >= d->OC && d->ld_out2 % 8 == 0 && d->epi == 0, "conv_igemm: bad out2");
@@ -1185,7 +1196,7 @@ static bool conv_plan_256(const wseg_conv_desc* d, Args& a, bool& ni7) {
   ni7 = false;
   // (OC % 256 != 0: only with a weight pack zero-padded to whole 256-row tiles, wseg_conv_desc.w_rows — the epilogue masks the columns >= OC)
   const bool oc_ok = d->OC % 256 == 0 || (d->in2 == nullptr && d->w_rows >= ((d->OC + 255) / 256) * 256);
-  if (!((d->dtype == WSEG_BF16 || (d->dtype == WSEG_F32X3 && d->in2 == nullptr)) && oc_ok && d->bm_hint != 64 && d->bm_hint != 128 &&
+  if (!((d->dtype == WSEG_BF16 || (d->dtype == WSEG_F32X3 && d->in2 == nullptr)) && oc_ok && d->epi != 3 && d->bm_hint != 64 && d->bm_hint != 128 &&
         d->bm_hint != 259 && d->bm_hint >= 0 && d->KH <= 8 && d->KW <= 8 && a.taps <= 16))   // (tap list: 16 four-bit entries; tap masks: 8 + 8 bits)
     return false;
   static const int auto256 = getenv("WSEG_CONV256") ? atoi(getenv("WSEG_CONV256")) : 1;   // (0: A/B switch — 128-tile kernel everywhere)
@@ -1225,11 +1236,11 @@ extern "C" int wseg_conv_igemm(const wseg_conv_desc* d, void* stream) {
 #define WSEG_LAUNCH_CONV(BM_)                                                                                   \
   do {                                                                                                          \
     if (d->dtype == WSEG_BF16) {                                                                                \
-      if (d->epi == 0) WSEG_LAUNCH_CONV1(WSEG_BF16, 0, BM_); else if (d->epi == 1) WSEG_LAUNCH_CONV1(WSEG_BF16, 1, BM_); else WSEG_LAUNCH_CONV1(WSEG_BF16, 2, BM_); \
+      if (d->epi == 0) WSEG_LAUNCH_CONV1(WSEG_BF16, 0, BM_); else if (d->epi == 1) WSEG_LAUNCH_CONV1(WSEG_BF16, 1, BM_); else if (d->epi == 2) WSEG_LAUNCH_CONV1(WSEG_BF16, 2, BM_); else WSEG_LAUNCH_CONV1(WSEG_BF16, 3, BM_); \
     } else if (d->dtype == WSEG_F32X3) {                                                                        \
-      if (d->epi == 0) WSEG_LAUNCH_CONV1(WSEG_F32X3, 0, BM_); else if (d->epi == 1) WSEG_LAUNCH_CONV1(WSEG_F32X3, 1, BM_); else WSEG_LAUNCH_CONV1(WSEG_F32X3, 2, BM_); \
+      if (d->epi == 0) WSEG_LAUNCH_CONV1(WSEG_F32X3, 0, BM_); else if (d->epi == 1) WSEG_LAUNCH_CONV1(WSEG_F32X3, 1, BM_); else if (d->epi == 2) WSEG_LAUNCH_CONV1(WSEG_F32X3, 2, BM_); else WSEG_LAUNCH_CONV1(WSEG_F32X3, 3, BM_); \
     } else {                                                                                                    \
-      if (d->epi == 0) WSEG_LAUNCH_CONV1(WSEG_F32, 0, BM_); else if (d->epi == 1) WSEG_LAUNCH_CONV1(WSEG_F32, 1, BM_); else WSEG_LAUNCH_CONV1(WSEG_F32, 2, BM_); \
+      if (d->epi == 0) WSEG_LAUNCH_CONV1(WSEG_F32, 0, BM_); else if (d->epi == 1) WSEG_LAUNCH_CONV1(WSEG_F32, 1, BM_); else if (d->epi == 2) WSEG_LAUNCH_CONV1(WSEG_F32, 2, BM_); else WSEG_LAUNCH_CONV1(WSEG_F32, 3, BM_); \
     }                                                                                                           \
   } while (0)
   // 256 x 256 (or 224 x 256) phase-pipelined tiles: bf16 / split-bf16, OC % 256 == 0, chosen by the CU-time model
@@ -1238,7 +1249,7 @@ extern "C" int wseg_conv_igemm(const wseg_conv_desc* d, void* stream) {
   if (big && a.nwg < 0) return -1;
   // 512 x 128 phase-pipelined tiles for OC = 128 layers with many pixels (259 forces it); fast taps only
   static const int auto512 = getenv("WSEG_CONV512") ? atoi(getenv("WSEG_CONV512")) : 1;   // (0: A/B switch; measured 649 -> 766 TF/s on 128->128 3x3 224^2)
-  const bool tall = !big && d->dtype == WSEG_BF16 && d->OC % 128 == 0 && (d->mode == 0 || d->stride == 1) &&
+  const bool tall = !big && d->dtype == WSEG_BF16 && d->epi != 3 && d->OC % 128 == 0 && (d->mode == 0 || d->stride == 1) &&
                     (d->bm_hint == 259 || (auto512 && d->bm_hint == 0 && d->OC == 128 && (M + 511) / 512 >= 512));
   if (tall) {
     WSEG_CHECK(d->IH <= 8000 && d->IW <= 8000 && d->OH <= 8000 && d->OW <= 8000 && d->pad <= 4096 && d->KH * d->dil <= 4096,

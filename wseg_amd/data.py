@@ -135,6 +135,24 @@ class VOC12ClsDataset(Dataset):                            # voc12/data.py:58-90
         return name, img, torch.from_numpy(self.label_list[idx])
 
 
+class VOC12ImageDataset(Dataset):                          # voc12/data.py:58-74: (name, image) without labels (aff_infer.py:58-62)
+    def __init__(self, img_name_list_path, voc12_root, transform=None):
+        self.img_name_list = load_img_name_list(img_name_list_path)
+        self.voc12_root = voc12_root
+        self.transform = transform
+
+    def __len__(self):
+        return len(self.img_name_list)
+
+    def __getitem__(self, idx):
+        name = self.img_name_list[idx]
+        img = PIL.Image.open(get_img_path(name, self.voc12_root)).convert("RGB")
+        if self.transform:
+            for t in self.transform:
+                img = t(img)
+        return name, img
+
+
 class VOC12ClsDatasetMSF(VOC12ClsDataset):                 # voc12/data.py:92-121
     def __init__(self, img_name_list_path, voc12_root, labels_path, scales, inter_transform=None, unit=1):
         super().__init__(img_name_list_path, voc12_root, labels_path, transform=None)

@@ -23,6 +23,7 @@ FUSE_SKIP = os.environ.get("WSEG_FUSE_SKIP", "1") != "0"   # bottleneck skip con
 FEAT_LD = 256          # PCM feature rows: [f8_3 64 | f8_4 128 | x_s 3 | zero pad 61]
 
 
+CONTRAST_FLAT_HEAD_ORDER = ("fc_proj", "fc8", "f8_3", "f8_4", "f9")
 DT_OF = {"bf16": L.BF16, "fp32": L.F32, "bf16x3": L.F32X3}   # bf16x3: f32 storage, conv / wgrad products as split-bf16 (3 bf16 MFMAs)
 
 
@@ -81,15 +82,15 @@ class Engine:
         return mod
 
     def trainable_order(self):
-        """Flat-buffer order: backbone convs b3..b7, then fc_proj, fc8 (adjacent: the fused head
-        GEMM's weight gradient is one [149,4096] block), f8_3, f8_4, f9."""
+        """Flat-buffer order: backbone convs b3..b7, then the net's FLAT_HEAD_ORDER — for the contrast net fc_proj, fc8
+        (adjacent: the fused head GEMM's weight gradient is one [149,4096] block), f8_3, f8_4, f9."""
         if self._order is None:
             names = []
             for b in arch.BLOCKS:
                 if b[0] in arch.FROZEN_BLOCKS:
                     continue
                 names += [c[0] for c in arch.block_convs(b)]
-            names += ["fc_proj", "fc8", "f8_3", "f8_4", "f9"]
+            names += list(getattr(self.net, "FLAT_HEAD_ORDER", CONTRAST_FLAT_HEAD_ORDER))
             self._order = names
         return self._order
 
@@ -311,6 +312,13 @@ class Engine:
                 for nm, buf in plan["fwd_bufs"].items():
                     P["w"][nm + ".skip_fused"] = buf
                 L.copy2d_batch(mirror, plan["fwd_flat"], plan["fwd_table"], plan["fwd_table"].shape[0], plan["fwd_chunks"])
+            if getattr(net, "HEAD_KIND", "contrast") == "aff":
+                # AffinityNet head (resnet38_aff.py:13-17): four plain 1x1 packs, views of the mirror like the backbone's (every row is whole
+                # 32-element groups, so the split-bf16 mirror holds them too)
+                for nm, (co, ci) in net.HEAD_CONVS.items():
+                    off, n = self.offsets[nm]
+                    P["w"][nm] = mirror[off:off + n].view(co, 1, ci)
+                return
             # fused head: rows [fc_proj | fc8 | 0]; its transposed pack is made from the two f32 masters directly
             hb = getattr(self, "_head_bufs", None)               # persistent: the zero padding (rows / columns 149..191) is written once
             if hb is None or hb[0] != (dt, str(device)):

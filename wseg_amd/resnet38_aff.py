@@ -1,0 +1,164 @@
+"""Drop-in replacement of the reference's AffinityNet module: `--network wseg_amd.resnet38_aff` (inference only).
+
+Mirrors the public contract of network/resnet38_aff.py (+ network/resnet38d.py:104-214): `Net()`, `forward(x, to_dense=False)`
+returning the pair affinities [N, P, n_from] (or, with to_dense, the dense [area, area] matrix of one image as a device tensor),
+`.normalize`, `.get_parameter_groups()`, and the reference's state_dict keys (the backbone, then f8_3, f8_4, f8_5, f9).  The
+sub-modules are parameter containers: the backbone runs through wseg_amd.engine (the contrast net's kernels and packs), the
+ELU head on the implicit-GEMM conv (epilogue 3), the pairs / dense scatter in csrc/affinity.hip.  Training (aff_train.py) is out
+of scope: a forward in training mode raises.
+"""
+import os
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import arch
+from . import engine
+from . import _lib as L
+from .resnet38_contrast import Net as _ContrastNet, Normalize, _Block
+
+FEAT_C = 448                                    # [f8_3 64 | f8_4 128 | f8_5 256]: the concat of resnet38_aff.py:47 is three column slices
+DEFAULT_RADIUS = 5
+PREDEFINED_FEATURESIZE = 448 // 8               # resnet38_aff.py:27-29 (the same pair set as the general rule at 56 x 56)
+
+
+def pair_radius(h, w, radius=DEFAULT_RADIUS):
+    """The radius rule of resnet38_aff.py:51-56: (min_edge - 1) // 2 below 2 * radius + 1, else `radius`.  The reference's pair set is empty
+    at radius 1 (min feature edge 3 or 4: its index construction fails), so a map whose min edge is below 5 is refused here."""
+    min_edge = min(h, w)
+    r = (min_edge - 1) // 2 if min_edge < radius * 2 + 1 else radius
+    if r < 2:
+        raise ValueError(f"AffinityNet needs a feature map with min edge >= 5 (an input side >= 33 px); got {h}x{w} (radius {r})")
+    return r
+
+
+def pair_offsets(radius):
+    """[(dy, dx)] in the reference's order (tool/pyutils.py get_indices_of_pairs)."""
+    out = [(0, x) for x in range(1, radius)]
+    for y in range(1, radius):
+        for x in range(-radius + 1, radius):
+            if x * x + y * y < radius * radius:
+                out.append((y, x))
+    return out
+
+
+def indices_of_pairs(radius, size):
+    """(ind_from [n_from], ind_to [P * n_from]) int64 — the pair set the kernels use, as flat pixel indices of an h x w map.
+    "from" pixels: rows [0, h-r+1) x columns [r-1, w-r+1)."""
+    h, w = size
+    rf = radius - 1
+    full = np.arange(h * w, dtype=np.int64).reshape(h, w)
+    ch, cw = h - rf, w - 2 * rf
+    ind_from = full[:ch, rf:rf + cw].reshape(-1)
+    ind_to = np.concatenate([full[dy:dy + ch, rf + dx:rf + dx + cw].reshape(-1) for dy, dx in pair_offsets(radius)])
+    return ind_from, ind_to
+
+
+class Net(nn.Module):
+    HEAD_KIND = "aff"
+    HEAD_CONVS = arch.AFF_HEAD_CONVS
+    FLAT_HEAD_ORDER = tuple(arch.AFF_HEAD_CONVS)
+
+    def __init__(self, precision=None):
+        super().__init__()
+        self.conv1a = nn.Conv2d(3, 64, 3, padding=1, bias=False)
+        for spec in arch.BLOCKS:
+            setattr(self, spec[0], _Block(spec))
+        self.bn7 = nn.BatchNorm2d(4096)
+        self.f8_3 = nn.Conv2d(512, 64, 1, bias=False)
+        self.f8_4 = nn.Conv2d(1024, 128, 1, bias=False)
+        self.f8_5 = nn.Conv2d(4096, 256, 1, bias=False)
+        self.f9 = nn.Conv2d(448, 448, 1, bias=False)
+        # inits of network/resnet38_aff.py:19-22
+        nn.init.kaiming_normal_(self.f8_3.weight)
+        nn.init.kaiming_normal_(self.f8_4.weight)
+        nn.init.kaiming_normal_(self.f8_5.weight)
+        nn.init.xavier_uniform_(self.f9.weight, gain=4)
+        self.not_training = [self.conv1a, self.b2, self.b2_1, self.b2_2]
+        self.from_scratch_layers = [self.f8_3, self.f8_4, self.f8_5, self.f9]
+        self.predefined_featuresize = PREDEFINED_FEATURESIZE
+        self.radius = DEFAULT_RADIUS
+        self.normalize = Normalize()
+        self.precision = precision or os.environ.get("WSEG_PRECISION", "bf16")
+        assert self.precision in ("bf16", "fp32", "bf16x3")
+
+    _engine = _ContrastNet._engine             # one engine per module instance (replicas get their own)
+
+    # ---- reference API -------------------------------------------------------------------
+    def forward(self, x, to_dense=False):
+        """network/resnet38_aff.py:40-97."""
+        if self.training:
+            raise RuntimeError("wseg_amd.resnet38_aff.Net is inference-only (aff_train is out of scope): call .eval() first")
+        aff, (h, w, r) = self.affinities(x)
+        if not to_dense:
+            return aff
+        if aff.shape[0] != 1:
+            raise ValueError("forward(x, to_dense=True) builds the matrix of ONE image (as the reference): batch size must be 1")
+        dense = torch.empty(h * w, h * w, device=aff.device, dtype=torch.float32)
+        L.aff_to_dense(aff, dense, h, w, r)
+        return dense
+
+    @torch.no_grad()
+    def affinities(self, x):
+        """(aff [N, P, n_from] f32, (h, w, radius)) on the HIP kernels; nothing synchronises."""
+        if not x.is_cuda:
+            raise RuntimeError("wseg_amd.resnet38_aff runs only on an MI355X (HIP) device; there is no CPU fallback")
+        x = x.contiguous().float()
+        eng = self._engine.active(x.device)
+        dt = engine.DT_OF[self.precision]
+        tdt = L.TORCH_DTYPE[dt]
+        eng.ensure_packs(x.device, dt)
+        st = eng._run_blocks([x], None, 0, len(arch.BLOCKS), False, None)       # conv4 / conv5 / conv6 (resnet38d.py:160-189)
+        eng._join_late_packs(x.device)
+        P = eng.packs
+        N = x.shape[0]
+        (h, w), = st["dims"]
+        r = pair_radius(h, w, self.radius)
+        M = N * h * w
+        cdt = engine._cdt(dt)
+
+        def conv(inp, name, out, cin, cout, ld_out):
+            L.conv_igemm(inp, P["w"][name], out, None, N=N, IH=h, IW=w, IC=cin, OH=h, OW=w, OC=cout, KH=1, KW=1,
+                         epi=3, ld_out=ld_out, dtype=cdt)
+
+        feat = torch.empty(M, FEAT_C, device=x.device, dtype=tdt)
+        conv(st["conv4"], "f8_3", feat, 512, 64, FEAT_C)
+        conv(st["conv5"], "f8_4", feat.view(-1)[64:], 1024, 128, FEAT_C)
+        conv(st["t"], "f8_5", feat.view(-1)[192:], 4096, 256, FEAT_C)
+        f9 = torch.empty(M, FEAT_C, device=x.device, dtype=tdt)
+        conv(feat, "f9", f9, FEAT_C, FEAT_C, FEAT_C)
+        n_from = (h - r + 1) * (w - 2 * r + 2)
+        aff = torch.empty(N, L.aff_num_offsets(r), n_from, device=x.device, dtype=torch.float32)
+        L.aff_pairs(f9, FEAT_C, FEAT_C, aff, N, h, w, r)
+        return aff, (h, w, r)
+
+    def get_parameter_groups(self):
+        """network/resnet38_aff.py:100-119."""
+        groups = ([], [], [], [])
+        for m in self.modules():
+            if isinstance(m, (nn.Conv2d, nn.modules.normalization.GroupNorm)):
+                if m.weight.requires_grad:
+                    (groups[2] if m in self.from_scratch_layers else groups[0]).append(m.weight)
+                if m.bias is not None and m.bias.requires_grad:
+                    (groups[3] if m in self.from_scratch_layers else groups[1]).append(m.bias)
+        return groups
+
+    def train(self, mode=True):
+        """network/resnet38d.py:192-214: frozen prefix + every BatchNorm in eval and frozen (forward still refuses training mode)."""
+        super().train(mode)
+        for layer in self.not_training:
+            if isinstance(layer, nn.Conv2d):
+                layer.weight.requires_grad = False
+            elif isinstance(layer, nn.Module):
+                for c in layer.children():
+                    if getattr(c, "weight", None) is not None:
+                        c.weight.requires_grad = False
+                    if getattr(c, "bias", None) is not None:
+                        c.bias.requires_grad = False
+        for layer in self.modules():
+            if isinstance(layer, nn.BatchNorm2d):
+                layer.eval()
+                layer.bias.requires_grad = False
+                layer.weight.requires_grad = False
+        return self

@@ -59,6 +59,10 @@ class Normalize:
 
 
 class Net(nn.Module):
+    HEAD_KIND = "contrast"                     # the engine's head table (arch.HEAD_CONVS) and flat-buffer order of the head weights
+    HEAD_CONVS = arch.HEAD_CONVS
+    FLAT_HEAD_ORDER = engine.CONTRAST_FLAT_HEAD_ORDER
+
     def __init__(self, precision=None):
         super().__init__()
         self.conv1a = nn.Conv2d(3, 64, 3, padding=1, bias=False)

@@ -10,7 +10,7 @@ from collections import OrderedDict
 
 import torch
 
-from .arch import state_dict_spec
+from .arch import AFF_HEAD_CONVS, state_dict_spec
 
 
 def hash_uniform(key, n, device="cpu"):
@@ -108,4 +108,39 @@ def synthetic_dropout_masks(n, seed=0, device="cpu"):
     for k, (c, p) in DROPOUT_SITES.items():
         keep = (_uniform("mask." + k, seed, (n, c), 0.0, 1.0, device) >= p).float() / (1.0 - p)
         out[k] = keep
+    return out
+
+
+AFF_HEAD_GAIN = {"f8_3": 1.0, "f8_4": 1.0, "f8_5": 1.0, "f9": 0.05}
+
+
+def procedural_aff_state_dict(seed=0, device="cpu"):
+    """State dict of the AffinityNet (network/resnet38_aff.py): the backbone entries of procedural_state_dict(seed), then the four
+    head convs, uniform with std gain*sqrt(2/fan_in) under keys of their own ("aff." + name: distinct from the contrast head's values).
+    f9's small gain keeps the mean |f_i - f_j| of its 448 ELU features O(0.1), so exp(-.)^beta spreads over (0, 1) instead of vanishing."""
+    sd = OrderedDict()
+    for k, shape in state_dict_spec(AFF_HEAD_CONVS).items():
+        head = k.split(".")[0]
+        if head in AFF_HEAD_CONVS:
+            cout, cin, kh, kw = shape
+            a = AFF_HEAD_GAIN[head] * (6.0 / (cin * kh * kw)) ** 0.5
+            sd[k] = _uniform("aff." + k, seed, shape, -a, a, device)
+        else:
+            sd[k] = procedural_tensor(k, shape, seed, device)
+    return sd
+
+
+def synthetic_cam_dict(H, W, classes, seed=0, device="cpu"):
+    """{class: float32 [H, W]} — what contrast_infer.py:82-90 writes per image (per-class normalised CAMs in [0, 1]), in closed form: per
+    class one anisotropic Gaussian bump (centre / widths from the hash) plus a small hash texture, scaled to a maximum of 1."""
+    out = {}
+    ys = torch.arange(H, dtype=torch.float32, device=device).view(H, 1)
+    xs = torch.arange(W, dtype=torch.float32, device=device).view(1, W)
+    for c in classes:
+        u = _uniform(f"cam{c}", seed, (4,), 0.0, 1.0).tolist()
+        cy, cx = u[0] * H, u[1] * W
+        sy, sx = (0.15 + 0.35 * u[2]) * H, (0.15 + 0.35 * u[3]) * W
+        m = torch.exp(-(((ys - cy) / sy) ** 2 + ((xs - cx) / sx) ** 2) * 0.5)
+        m = m + 0.05 * _uniform(f"camtex{c}", seed, (H, W), 0.0, 1.0, device)
+        out[int(c)] = (m / m.max()).to(torch.float32)
     return out
