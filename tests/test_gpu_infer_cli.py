@@ -234,6 +234,15 @@ def test_prototype_merge_eight_ranks():
     rv, rf, rc = local_candidates(ncam, feat, K, tie.long())
     ref = merge(rv[None], rf[None], rc[None])
     np.testing.assert_allclose(p8.cpu().numpy(), ref.numpy(), rtol=1e-5, atol=1e-6)
+    # a NaN candidate value (a diverged rank) ranks as -inf: at world 8 it falls out of the top K and no index leaves the lists
+    cvs[2][5, 0] = float("nan")
+    p8n = torch.empty(21, 128, device=dev)
+    L.proto_merge(torch.stack(cvs), torch.stack(cfs), torch.stack(ccs), p8n, world, K)
+    vals = torch.stack(cvs).cpu()
+    vals[torch.isnan(vals)] = float("-inf")
+    refn = merge(vals, torch.stack(cfs).cpu(), torch.stack(ccs).cpu().bool())
+    assert bool(torch.isfinite(p8n.cpu()).all())
+    np.testing.assert_allclose(p8n.cpu().numpy(), refn.numpy(), rtol=1e-5, atol=1e-6)
 
 
 @pytest.mark.parametrize("img_hw,crop,prec,dev_aug", [((96, 128), 128, "bf16", False), ((448, 448), 448, "fp32", False), ((375, 500), 448, "bf16x3", True)])

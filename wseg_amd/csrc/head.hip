@@ -132,10 +132,15 @@ __global__ void resize_planar_bwd_kernel(const float* __restrict__ d_out, float*
   const int x = (int)(idx % iw); const long r = idx / iw;
   const int y = (int)(r % ih); const long pl = r / ih;
   const float sy = resize_scale(ih, oh, align), sx = resize_scale(iw, ow, align);
-  // candidate output range: source coordinate within (y-1, y+1)
+  // candidate output range: source coordinate within (y-1, y+1), widened by one output for rounding.
+  // align: s = sy*o  -> o in ((y-1)/sy, (y+1)/sy);   !align: s = sy*(o+0.5)-0.5  -> o in ((y-0.5)/sy-0.5, (y+1.5)/sy-0.5)
   int oy_lo, oy_hi, ox_lo, ox_hi;
-  if (sy > 0.f) { oy_lo = max(0, (int)floorf((y - 1) / sy) - 1); oy_hi = min(oh - 1, (int)ceilf((y + 1) / sy) + 1); } else { oy_lo = 0; oy_hi = oh - 1; }
-  if (sx > 0.f) { ox_lo = max(0, (int)floorf((x - 1) / sx) - 1); ox_hi = min(ow - 1, (int)ceilf((x + 1) / sx) + 1); } else { ox_lo = 0; ox_hi = ow - 1; }
+  if (!(sy > 0.f)) { oy_lo = 0; oy_hi = oh - 1; }
+  else if (align) { oy_lo = max(0, (int)floorf((y - 1) / sy) - 1); oy_hi = min(oh - 1, (int)ceilf((y + 1) / sy) + 1); }
+  else { oy_lo = max(0, (int)floorf((y - 0.5f) / sy - 0.5f) - 1); oy_hi = min(oh - 1, (int)ceilf((y + 1.5f) / sy - 0.5f) + 1); }
+  if (!(sx > 0.f)) { ox_lo = 0; ox_hi = ow - 1; }
+  else if (align) { ox_lo = max(0, (int)floorf((x - 1) / sx) - 1); ox_hi = min(ow - 1, (int)ceilf((x + 1) / sx) + 1); }
+  else { ox_lo = max(0, (int)floorf((x - 0.5f) / sx - 0.5f) - 1); ox_hi = min(ow - 1, (int)ceilf((x + 1.5f) / sx - 0.5f) + 1); }
   const float* g = d_out + (size_t)pl * oh * ow;
   const float gadd = plane_add ? plane_add[pl] : 0.f;      // a constant added to every d_out element of the plane
   float acc = 0.f;

@@ -472,7 +472,8 @@ __global__ __launch_bounds__(256) void proto_candidates_kernel(const float* __re
   float lmx = -INFINITY, lmn = INFINITY;
   for (int p = tid; p < P; p += 256) {
     const int n = p / npix, pix = p - n * npix;
-    const float v = ncam[((size_t)n * 21 + c) * npix + pix];
+    float v = ncam[((size_t)n * 21 + c) * npix + pix];
+    if (v != v) v = -INFINITY;                             // NaN ranks as -inf (a diverged step: the class prototype turns NaN below)
     sv[p] = v; lmx = fmaxf(lmx, v); lmn = fminf(lmn, v);
   }
   r_v[tid] = lmx; __syncthreads();
@@ -484,10 +485,12 @@ __global__ __launch_bounds__(256) void proto_candidates_kernel(const float* __re
   __syncthreads();
   const bool is_const = (gmx == s_gmin);
   if (is_const) {
-    if (tid < K) sel[tid] = tie_idx[tid];
+    if (tid < K) sel[tid] = min(max(tie_idx[tid], 0), P - 1);
     __syncthreads();
   } else {
-    for (int k = 0; k < K; ++k) {                          // K rounds of (max value, lowest index): wave shuffles + one LDS hop
+    // K rounds of (max value, lowest index): wave shuffles + one LDS hop.  A taken value becomes NaN, which no compare
+    // selects again; every value left is >= -inf, so while K <= P each round finds an index (bi < P).
+    for (int k = 0; k < K; ++k) {
       float bv = -INFINITY; int bi = 0x7fffffff;
       for (int p = tid; p < P; p += 256) { const float v = sv[p]; if (v > bv || (v == bv && p < bi)) { bv = v; bi = p; } }
 #pragma unroll
@@ -500,7 +503,8 @@ __global__ __launch_bounds__(256) void proto_candidates_kernel(const float* __re
       if (tid == 0) {
 #pragma unroll
         for (int w = 1; w < 4; ++w) if (r_v[w] > bv || (r_v[w] == bv && r_i[w] < bi)) { bv = r_v[w]; bi = r_i[w]; }
-        sel[k] = bi; sv[bi] = -INFINITY;
+        if (bi >= P) bi = 0;                               // (unreachable: no sentinel reaches an address)
+        sel[k] = bi; sv[bi] = NAN;
       }
       __syncthreads();
     }
@@ -519,15 +523,19 @@ __global__ __launch_bounds__(128) void proto_merge_kernel(const float* __restric
   __shared__ float vals[512]; __shared__ int order[64]; __shared__ float red[2]; __shared__ int cst_s;
   const int c = blockIdx.x, tid = threadIdx.x;
   const int M = world * K;                                  // rank w's [21][K] values / [21][K][128] features / [21] flags at w * rs_*
-  for (int i = tid; i < M; i += 128) { const int w = i / K, k = i - w * K; vals[i] = cand_val[(size_t)w * rs_val + c * K + k]; }
+  for (int i = tid; i < M; i += 128) {
+    const int w = i / K, k = i - w * K;
+    const float v = cand_val[(size_t)w * rs_val + c * K + k];
+    vals[i] = v != v ? -INFINITY : v;                       // NaN ranks as -inf: the compares below then order every pair
+  }
+  if (tid < K) order[tid] = tid;                            // (every slot holds a valid index even before the ranking)
   if (tid == 0) {
     bool cst = true;
     for (int w = 0; w < world; ++w) cst = cst && cand_const[(size_t)w * rs_const + c];
     cst_s = cst ? 1 : 0;
   }
   __syncthreads();
-  if (cst_s) { if (tid < K) order[tid] = tid; }             // fully tied: rank 0's set (global pixels first)
-  else {
+  if (!cst_s) {                                             // (fully tied: rank 0's set, global pixels first: order[] as initialised)
     // rank by counting (round 2 selected serially on one thread: K x M compares, 40 us at world 8): candidate i is the
     // (#{j : v_j > v_i or (v_j == v_i and j < i)})-th largest — the order of K rounds of "first maximum"
     for (int i = tid; i < M; i += 128) {
