@@ -21,8 +21,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from wseg_amd import _lib as L, arch, synth  # noqa: E402
-from wseg_amd.engine import DT_OF  # noqa: E402
+from wseg_amd import _lib as L, synth  # noqa: E402
 from wseg_amd.resnet38_aff import Net, pair_radius  # noqa: E402
 
 
@@ -56,8 +55,7 @@ def main():
     assert r == pair_radius(h, w)
 
     def backbone_head():
-        eng.ensure_packs(x.device, DT_OF[m.precision])
-        return eng._run_blocks([x], None, 0, len(arch.BLOCKS), False, None)
+        return eng.run_backbone([x])
 
     for _ in range(3):
         m.affinities(x)

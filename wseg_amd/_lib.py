@@ -3,6 +3,7 @@
 There is deliberately NO fallback: if the library is missing the import raises, and every
 wrapper raises RuntimeError(wseg_last_error()) on a non-zero status.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -65,8 +66,8 @@ def _load():
     lib = C.CDLL(LIB_PATH)
     lib.wseg_last_error.restype = C.c_char_p
     lib.wseg_version.restype = C.c_int
-    lib.wseg_sizeof_conv_desc.restype = C.c_size_t
-    lib.wseg_sizeof_wgrad_desc.restype = C.c_size_t
+    for fn in ("wseg_sizeof_conv_desc", "wseg_sizeof_wgrad_desc", "wseg_select_workspace_bytes", "wseg_plane_stats_workspace_bytes"):
+        getattr(lib, fn).restype = C.c_size_t
     if lib.wseg_sizeof_conv_desc() != C.sizeof(ConvDesc) or lib.wseg_sizeof_wgrad_desc() != C.sizeof(WgradDesc):
         raise ImportError(f"{LIB_PATH} was built from another include/wseg_hip.h (descriptor sizes "
                           f"{lib.wseg_sizeof_conv_desc()}/{lib.wseg_sizeof_wgrad_desc()} vs {C.sizeof(ConvDesc)}/{C.sizeof(WgradDesc)}): rebuild it")
@@ -89,6 +90,23 @@ def check(status, what):
         raise RuntimeError(f"{what} failed ({status}): {lib.wseg_last_error().decode()}")
 
 
+def _v(x):
+    return C.c_void_p(_ptr(x))
+
+
+def _s():
+    return C.c_void_p(stream_ptr())
+
+
+def _f(x):
+    return C.c_float(x)
+
+
+def _call(name, *args):
+    """lib.<name>(*args, current stream), raising on a non-zero status"""
+    check(getattr(lib, name)(*args, _s()), name)
+
+
 def dtype_code(t):
     if t.dtype == torch.float32:
         return F32
@@ -98,6 +116,30 @@ def dtype_code(t):
 
 
 TRACK_PAIRS, LAST_PAIR_FUSED = False, None        # tests: whether the last pair_wgrad launch was ONE grid
+
+
+def _flops_label(kind, *, N, IH, IW, IC, OH, OW, OC, KH, KW, stride=1, dil=1, seg2=None, mode=0, IC2=None, **_):
+    """(algorithmic FLOPs, label) of a conv / wgrad launch for the profiler.  Pixels counted: the CONV's output pixels — the launch's
+    input side for a data gradient (mode 1); IC2: channels of a second source."""
+    oh, ow = (OH, OW) if mode == 0 else (IH, IW)
+    pix = N * oh * ow
+    if seg2 is not None:
+        pix += N * (seg2[2] * seg2[3] if mode == 0 else seg2[0] * seg2[1])
+    kin = IC * KH * KW + (IC2 or 0)
+    return 2.0 * pix * kin * OC, f"{kind} {IC}{('+%d' % IC2) if IC2 else ''}->{OC} k{KH} s{stride} d{dil} {OH}x{OW}"
+
+
+@contextlib.contextmanager
+def _timed(sink, entry):
+    """Bracket a launch with HIP events on its stream and append (ev0, ev1, *entry()) to `sink`; sink None: just run it."""
+    if sink is None:
+        yield
+        return
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    yield
+    ev1.record()
+    sink.append((ev0, ev1) + tuple(entry()))
 
 
 def conv_igemm(inp, w, out=None, out2=None, *, N, IH, IW, IC, OH, OW, OC, KH, KW, stride=1, dil=1, pad=0,
@@ -117,35 +159,31 @@ def conv_igemm(inp, w, out=None, out2=None, *, N, IH, IW, IC, OH, OW, OC, KH, KW
     d.mode, d.epi, d.dtype, d.relu_out2, d.relu_lt, d.bm_hint = mode, epi, (dtype_code(inp) if dtype is None else dtype), relu_out2, relu_lt, bm_hint
     if seg2 is not None:                         # (IH2, IW2, OH2, OW2): second row segment, same N
         d.IH2, d.IW2, d.OH2, d.OW2 = seg2
-    if in2 is not None:                          # two sources: w = [OC][KH*KW*IC + IC2]
-        d.in2, d.IC2, d.ld_in2 = _ptr(in2), IC2, ld_in2 or (IC2 or IC)
-    krow = KH * KW * IC + ((IC2 or IC) if in2 is not None else 0)
+    ic2 = (IC2 or IC) if in2 is not None else 0  # two sources: w = [OC][KH*KW*IC + IC2]
+    if in2 is not None:
+        d.in2, d.IC2, d.ld_in2 = _ptr(in2), IC2, ld_in2 or ic2
+    krow = KH * KW * IC + ic2
     d.w_rows = w_rows
     if w.numel() < max(OC, w_rows) * krow:       # (raw pointers beyond this line: a short weight buffer would be read out of bounds)
         raise RuntimeError(f"conv_igemm: weight buffer has {w.numel()} elements, the launch reads {max(OC, w_rows)} x {krow}")
     sampled, launch_idx = _profile_sample() if PROFILE is not None else (False, 0)
-    if sampled:                                  # bench.py: HIP events on the launch stream around this launch
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    wflops = 0.0
-    if pair_wgrad is not None:
-        wx, wdy, wdw, wkw = pair_wgrad
-        wd = _wgrad_desc(wx, wdy, wdw, **wkw)
-        global LAST_PAIR_FUSED
-        LAST_PAIR_FUSED = lib.wseg_conv_bwd_pair_fuses(C.byref(d), C.byref(wd)) if TRACK_PAIRS else None
-        check(lib.wseg_conv_bwd_pair(C.byref(d), C.byref(wd), C.c_void_p(stream_ptr())), "wseg_conv_bwd_pair")
-        wpix = wkw["N"] * wkw["OH"] * wkw["OW"] + (wkw["N"] * wkw["seg2"][2] * wkw["seg2"][3] if wkw.get("seg2") is not None else 0)
-        wflops = 2.0 * wpix * wkw["IC"] * wkw["OC"] * wkw["KH"] * wkw["KW"]
-    else:
-        check(lib.wseg_conv_igemm(C.byref(d), C.c_void_p(stream_ptr())), "wseg_conv_igemm")
-    if sampled:
-        ev1.record()
-        pix = N * (OH * OW if mode == 0 else IH * IW)        # algorithmic: the conv's output pixels
-        if seg2 is not None:
-            pix += N * (seg2[2] * seg2[3] if mode == 0 else seg2[0] * seg2[1])
-        kin = IC * KH * KW + ((IC2 or IC) if in2 is not None else 0)
-        PROFILE.append((ev0, ev1, 2.0 * pix * kin * OC + wflops,
-                        f"{'fwd' if mode == 0 else ('dgrad+wgrad' if pair_wgrad is not None else 'dgrad')} {IC}{('+%d' % (IC2 or IC)) if in2 is not None else ''}->{OC} k{KH} s{stride} d{dil} {OH}x{OW}", launch_idx))
+
+    def entry():
+        kind = "fwd" if mode == 0 else ("dgrad+wgrad" if pair_wgrad is not None else "dgrad")
+        flops, label = _flops_label(kind, N=N, IH=IH, IW=IW, IC=IC, OH=OH, OW=OW, OC=OC, KH=KH, KW=KW, stride=stride, dil=dil, seg2=seg2,
+                                    mode=mode, IC2=ic2)
+        wflops = _flops_label("wgrad", **pair_wgrad[3])[0] if pair_wgrad is not None else 0.0
+        return flops + wflops, label, launch_idx
+
+    with _timed(PROFILE if sampled else None, entry):        # bench.py: HIP events on the launch stream around this launch
+        if pair_wgrad is not None:
+            wx, wdy, wdw, wkw = pair_wgrad
+            wd = _wgrad_desc(wx, wdy, wdw, **wkw)
+            global LAST_PAIR_FUSED
+            LAST_PAIR_FUSED = lib.wseg_conv_bwd_pair_fuses(C.byref(d), C.byref(wd)) if TRACK_PAIRS else None
+            _call("wseg_conv_bwd_pair", C.byref(d), C.byref(wd))
+        else:
+            _call("wseg_conv_igemm", C.byref(d))
 
 
 def _wgrad_desc(x, dy, dw, *, N, IH, IW, IC, OH, OW, OC, KH, KW, stride=1, dil=1, pad=0,
@@ -164,66 +202,41 @@ def _wgrad_desc(x, dy, dw, *, N, IH, IW, IC, OH, OW, OC, KH, KW, stride=1, dil=1
     return d
 
 
-def conv_wgrad(x, dy, dw, *, N, IH, IW, IC, OH, OW, OC, KH, KW, stride=1, dil=1, pad=0,
-               ld_x=None, ld_dy=None, split_k=0, IC_dw=None, OC_dw=None, tile_hint=0, seg2=None, dtype=None, dw_rot=0):
-    d = _wgrad_desc(x, dy, dw, N=N, IH=IH, IW=IW, IC=IC, OH=OH, OW=OW, OC=OC, KH=KH, KW=KW, stride=stride, dil=dil, pad=pad, ld_x=ld_x, ld_dy=ld_dy,
-                    split_k=split_k, IC_dw=IC_dw, OC_dw=OC_dw, tile_hint=tile_hint, seg2=seg2, dtype=dtype, dw_rot=dw_rot)
-    assert dw.dtype == torch.float32
-    if PROFILE_WGRAD is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(lib.wseg_conv_wgrad(C.byref(d), C.c_void_p(stream_ptr())), "wseg_conv_wgrad")
-    if PROFILE_WGRAD is not None:
-        ev1.record()
-        pix = N * OH * OW + (N * seg2[2] * seg2[3] if seg2 is not None else 0)
-        PROFILE_WGRAD.append((ev0, ev1, 2.0 * pix * IC * OC * KH * KW, f"wgrad {IC}->{OC} k{KH} s{stride} d{dil} {OH}x{OW}"))
+def conv_wgrad(x, dy, dw, **kw):
+    """dw += the weight gradient of the conv described by `kw` (the keywords of _wgrad_desc)"""
+    d = _wgrad_desc(x, dy, dw, **kw)
+    with _timed(PROFILE_WGRAD, lambda: _flops_label("wgrad", **kw)):
+        _call("wseg_conv_wgrad", C.byref(d))
 
 
 def pack_weights(master, fwd, tr, OC, T, IC, OCp, ICp, dtype, ic_rot=0):
-    check(lib.wseg_pack_weights(C.c_void_p(_ptr(master)), C.c_void_p(_ptr(fwd)), C.c_void_p(_ptr(tr)),
-                                OC, T, IC, OCp, ICp, ic_rot, dtype, C.c_void_p(stream_ptr())), "wseg_pack_weights")
+    _call("wseg_pack_weights", _v(master), _v(fwd), _v(tr), OC, T, IC, OCp, ICp, ic_rot, dtype)
 
 
 def copy2d_batch(src, dst, table, npieces, total_chunks):
-    check(lib.wseg_copy2d_batch(C.c_void_p(_ptr(src)), C.c_void_p(_ptr(dst)), C.c_void_p(_ptr(table)), npieces, C.c_long(total_chunks),
-                                C.c_void_p(stream_ptr())), "wseg_copy2d_batch")
+    _call("wseg_copy2d_batch", _v(src), _v(dst), _v(table), npieces, C.c_long(total_chunks))
 
 
 def pack_transposed_batch(master, out, table, nlayers, total_tiles, dtype):
-    check(lib.wseg_pack_transposed_batch(C.c_void_p(_ptr(master)), C.c_void_p(_ptr(out)), C.c_void_p(_ptr(table)), nlayers,
-                                         C.c_long(total_tiles), dtype, C.c_void_p(stream_ptr())), "wseg_pack_transposed_batch")
+    _call("wseg_pack_transposed_batch", _v(master), _v(out), _v(table), nlayers, C.c_long(total_tiles), dtype)
 
 
 def pack_transposed_batch_bf16(mirror, out, table, nlayers, total_tiles):
-    check(lib.wseg_pack_transposed_batch_bf16(C.c_void_p(_ptr(mirror)), C.c_void_p(_ptr(out)), C.c_void_p(_ptr(table)), nlayers,
-                                              C.c_long(total_tiles), C.c_void_p(stream_ptr())), "wseg_pack_transposed_batch_bf16")
+    _call("wseg_pack_transposed_batch_bf16", _v(mirror), _v(out), _v(table), nlayers, C.c_long(total_tiles))
 
 
 def dropout_scale(u, out, split_at, p0, p1):
-    check(lib.wseg_dropout_scale(C.c_void_p(_ptr(u)), C.c_void_p(_ptr(out)), C.c_long(u.numel()), C.c_long(split_at),
-                                 C.c_float(p0), C.c_float(p1), C.c_void_p(stream_ptr())), "wseg_dropout_scale")
+    _call("wseg_dropout_scale", _v(u), _v(out), C.c_long(u.numel()), C.c_long(split_at), _f(p0), _f(p1))
 
 
 def stem_conv_kc(x, w_kc, scale, shift, raw, act, N, H, W, dtype):
     if w_kc.numel() != 27 * 64 or w_kc.dtype != torch.float32:
         raise RuntimeError("stem_conv_kc: weights must be f32 [27][64]")
-    check(lib.wseg_stem_conv_kc(C.c_void_p(_ptr(x)), C.c_void_p(_ptr(w_kc)), C.c_void_p(_ptr(scale)), C.c_void_p(_ptr(shift)),
-                                C.c_void_p(_ptr(raw)), C.c_void_p(_ptr(act)), N, H, W, dtype,
-                                C.c_void_p(stream_ptr())), "wseg_stem_conv_kc")
+    _call("wseg_stem_conv_kc", _v(x), _v(w_kc), _v(scale), _v(shift), _v(raw), _v(act), N, H, W, dtype)
 
 
 def stem_conv(x, w, scale, shift, raw, act, N, H, W, dtype):
-    check(lib.wseg_stem_conv(C.c_void_p(_ptr(x)), C.c_void_p(_ptr(w)), C.c_void_p(_ptr(scale)), C.c_void_p(_ptr(shift)),
-                             C.c_void_p(_ptr(raw)), C.c_void_p(_ptr(act)), N, H, W, dtype,
-                             C.c_void_p(stream_ptr())), "wseg_stem_conv")
-
-
-def _v(x):
-    return C.c_void_p(_ptr(x))
-
-
-def _s():
-    return C.c_void_p(stream_ptr())
+    _call("wseg_stem_conv", _v(x), _v(w), _v(scale), _v(shift), _v(raw), _v(act), N, H, W, dtype)
 
 
 def head_split(head, ld, c0, cam_low, cmax, N, hw):
@@ -281,20 +294,6 @@ def sgd_step(params, grads, buf, segs, momentum, grad_scale, first_step, bf16_mi
 
 
 # ---------------------------------------------------------------------------------------------- loss kernels
-lib.wseg_select_workspace_bytes.restype = C.c_size_t
-
-
-def _call(name, *args):
-    check(getattr(lib, name)(*args, _s()), name)
-
-
-def _f(x):
-    return C.c_float(x)
-
-
-lib.wseg_plane_stats_workspace_bytes.restype = C.c_size_t
-
-
 def plane_stats(U, stats, planes, npix):
     ws = torch.empty(int(lib.wseg_plane_stats_workspace_bytes(C.c_long(planes))), device=U.device, dtype=torch.uint8)
     _call("wseg_plane_stats", _v(U), _v(stats), C.c_long(planes), npix, _v(ws))

@@ -116,9 +116,13 @@ def state_dict_spec(head_convs=None):
     return spec
 
 
-def _osz(h, k, s, d):
-    p = d * (k // 2)
-    return (h + 2 * p - d * (k - 1) - 1) // s + 1
+def block_out_dims(b, dims):
+    """Output (h, w) of block `b` for each input (h, w) of `dims`.  Every conv of a block produces this size: the strided conv is the
+    block's first one (3x3 at first_dilation in a ResBlock, 1x1 in a ResBlock_bot), padded by dilation * (k // 2)."""
+    name, kind, cin, mid, cout, stride, fd, d, p = b
+    k, dil = (3, fd) if kind == "res" else (1, 1)
+    span = 2 * (dil * (k // 2)) - dil * (k - 1) - 1
+    return [((h + span) // stride + 1, (w + span) // stride + 1) for (h, w) in dims]
 
 
 def forward_macs(H, W, head_convs=None):
@@ -129,9 +133,7 @@ def forward_macs(H, W, head_convs=None):
     macs = 3 * 64 * 9 * H * W                                   # conv1a, stride 1, same size
     h, w = H, W
     for b in BLOCKS:
-        name, kind, cin, mid, cout, stride, fd, d, p = b
-        k0, d0 = (3, fd) if kind == "res" else (1, 1)
-        oh, ow = _osz(h, k0, stride, d0), _osz(w, k0, stride, d0)
+        (oh, ow), = block_out_dims(b, [(h, w)])
         for (_n, ci, co, k, s, dd) in block_convs(b):
             macs += ci * co * k * k * oh * ow                   # every conv of a block produces the block's output size
         h, w = oh, ow

@@ -9,9 +9,9 @@ of network/resnet38d.py:160-189 and network/resnet38_contrast.py:31-75.  Activat
 The whole network is one torch.autograd.Function: its backward runs the hand-written dgrad /
 wgrad / PCM-backward kernels and accumulates straight into the flat gradient buffer.
 """
-import os
 import threading
 import weakref
+from typing import NamedTuple
 
 import torch
 
@@ -19,7 +19,6 @@ from . import arch
 from . import _lib as L
 
 HEAD_LD = 192          # fused head rows: [f_proj 128 | cam 21 | zero pad 43]  (a 256-wide row for the 256-tile kernels measured slower: profiles/HISTORY.md)
-FUSE_SKIP = os.environ.get("WSEG_FUSE_SKIP", "1") != "0"   # bottleneck skip conv + last conv as one two-source launch (bf16)
 FEAT_LD = 256          # PCM feature rows: [f8_3 64 | f8_4 128 | x_s 3 | zero pad 61]
 
 
@@ -32,9 +31,54 @@ def _cdt(dt):
     return L.F32X3 if dt == L.F32X3 else None
 
 
-def _out_size(h, k, s, d):
-    p = d * (k // 2)
-    return (h + 2 * p - d * (k - 1) - 1) // s + 1
+class Conv(NamedTuple):
+    """One conv layer over the batched views, described once.  name: the key of its pack in P["w"] / P["wt"] (for a weight gradient: the parameter's
+    name); din / dout: [(h, w)] per view of its input / output.  The three methods are the geometry keywords of L.conv_igemm / L.conv_wgrad."""
+    name: str
+    cin: int
+    cout: int
+    k: int
+    stride: int
+    dil: int
+    din: list
+    dout: list
+
+    def _kw(self, N, ic, oc, di, do):
+        seg2 = (di[1][0], di[1][1], do[1][0], do[1][1]) if len(di) == 2 else None        # the second view's row segment
+        return dict(N=N, IH=di[0][0], IW=di[0][1], IC=ic, OH=do[0][0], OW=do[0][1], OC=oc, KH=self.k, KW=self.k,
+                    stride=self.stride, dil=self.dil, pad=self.dil * (self.k // 2), seg2=seg2)
+
+    def fwd_kw(self, N):
+        return self._kw(N, self.cin, self.cout, self.din, self.dout)
+
+    def dgrad_kw(self, N):
+        """in = dY over the conv's OUTPUT dims, out = dX over its INPUT dims"""
+        return dict(self._kw(N, self.cout, self.cin, self.dout, self.din), mode=1)
+
+    wgrad_kw = fwd_kw                                       # (x over din, dY over dout: the forward geometry)
+
+
+class _Pass:
+    """What the launches of one pass share: batch size, device, precision mode and packs."""
+
+    def __init__(self, N, dev, dt, P):
+        self.N, self.dev, self.dt, self.P = N, dev, dt, P
+
+    def rows_of(self, dims):
+        return sum(self.N * h * w for (h, w) in dims)
+
+    def offs_of(self, dims):
+        o, out = 0, []
+        for (h, w) in dims:
+            out.append(o)
+            o += self.N * h * w
+        return out
+
+    def E(self, m, c):
+        return torch.empty((m, c), device=self.dev, dtype=L.TORCH_DTYPE[self.dt])
+
+    def conv(self, c, inp, out, out2=None, **kw):
+        L.conv_igemm(inp, self.P["w"][c.name], out, out2, dtype=_cdt(self.dt), **c.fwd_kw(self.N), **kw)
 
 
 class Engine:
@@ -60,6 +104,19 @@ class Engine:
         self.block_done_hook = None         # called with the block name when all of its weight gradients are enqueued
         self.capture_ctx = False            # tests: keep the saved forward context of the last training pass in `last_ctx`
         self.last_ctx = None
+        self.last_loss_views = None         # tests: loss_hip.step's per-view intermediates of the last step (capture_ctx)
+        self.offsets = None                 # {parameter name: (offset, numel)} in the flat buffers (ensure_flat)
+        self.flat_w3 = None                 # bf16x3: split-bf16 pack of flat_w
+        self.flat_wt = self.flat_wt3 = None     # transposed (dgrad) packs, flat; their batch tables below
+        self._wt_table = self._wt_table64 = None
+        self._wt_tiles = self._wt_tiles64 = 0
+        self._wt_pending = None             # (dt, mirror) until finish_packs has made the transposed packs
+        self._frozen_packs = self._frozen_key = None
+        self._head_bufs = None
+        self._fused = None                  # _fused_plan
+        self._late_ev = None                # event of the late packs until the forward pass has waited for it
+        self._mirror_pversions = None
+        self._streams = {}                  # role -> side stream (stream())
 
     @property
     def net(self):
@@ -154,7 +211,7 @@ class Engine:
 
     def _mirror_fresh(self, names):
         """False when a parameter was modified through torch (load_state_dict, manual edits) since the mirror was written."""
-        return getattr(self, "_mirror_pversions", None) == tuple(self.conv_param(n_)._version for n_ in names)
+        return self._mirror_pversions == tuple(self.conv_param(n_)._version for n_ in names)
 
     def grad_buckets(self, after=("b7", "b5", "b4", "b3")):
         """Contiguous slices of flat_g in the order backward completes them: {block name: (begin, end)} — the slice is
@@ -171,11 +228,28 @@ class Engine:
         assert end == 0, "the last bucket must reach the start of the flat buffer"
         return out
 
-    def grad_view(self, name):
+    def grad_slice(self, name, numel=None):
+        """The flat-gradient elements of parameter `name` (numel: a longer run that starts there)"""
         off, n = self.offsets[name]
-        p = self.conv_param(name)
-        oc, ic, kh, kw = p.shape
-        return self.flat_g[off:off + n].view(oc, kh, kw, ic).permute(0, 3, 1, 2)
+        return self.flat_g[off:off + (numel or n)]
+
+    def grad_view(self, name):
+        oc, ic, kh, kw = self.conv_param(name).shape
+        return self.grad_slice(name).view(oc, kh, kw, ic).permute(0, 3, 1, 2)
+
+    def stream(self, role, device):
+        """The side stream of `role` on `device`, created on first use: HIP maps streams onto four hardware queues in creation order, and
+        that layout moves the step time, so nothing creates one ahead of its first use."""
+        st = self._streams.get(role)
+        if st is None or st.device != device:
+            st = self._streams[role] = torch.cuda.Stream(device)
+        return st
+
+    def _flat_like(self, buf, dtype, device):
+        """`buf` when it is a flat_w-sized buffer of this dtype on this device, else a new (uninitialised) one"""
+        if buf is not None and buf.dtype == dtype and buf.device == device and buf.numel() == self.flat_w.numel():
+            return buf
+        return torch.empty(self.flat_w.numel(), device=device, dtype=dtype)
 
     def attach_grads(self):
         """Make every trainable p.grad a view of flat_g (zeroing it if the caller dropped the grads,
@@ -230,7 +304,7 @@ class Engine:
         net = self.net
         tdt = L.TORCH_DTYPE[dt]
         fkey = self.frozen_key(device, dt)
-        if getattr(self, "_frozen_packs", None) is None or self._frozen_key != fkey:
+        if self._frozen_packs is None or self._frozen_key != fkey:
             F_ = {"w": {}, "bn": {}}
             for b in arch.BLOCKS:
                 for (bname, c) in arch.block_bns(b):
@@ -253,25 +327,24 @@ class Engine:
         # forward packs [OC][T][IC] have exactly the layout of the flat master buffer: in f32 mode they ARE views of
         # it, in bf16 mode they are views of ONE cast copy (a single launch instead of one per layer)
         if dt == L.BF16:
-            if getattr(self, "flat_wb", None) is None or self.flat_wb.numel() != self.flat_w.numel() or self.flat_wb.device != device:
-                self.flat_wb = torch.empty(self.flat_w.numel(), device=device, dtype=torch.bfloat16)
-                self.flat_wb_version = None
+            wb = self._flat_like(self.flat_wb, torch.bfloat16, device)
+            if wb is not self.flat_wb:
+                self.flat_wb, self.flat_wb_version = wb, None
             if self.flat_wb_version != self.flat_w_version or not self._mirror_fresh(names):
                 L.to_bf16(self.flat_w, self.flat_wb)             # (normally the fused SGD step has already written it)
                 self.flat_wb_version = self.flat_w_version
             self._mirror_pversions = tuple(self.conv_param(n_)._version for n_ in names)
             mirror = self.flat_wb
         elif dt == L.F32X3:
-            if getattr(self, "flat_w3", None) is None or self.flat_w3.numel() != self.flat_w.numel() or self.flat_w3.device != device:
-                self.flat_w3 = torch.empty_like(self.flat_w)
+            self.flat_w3 = self._flat_like(self.flat_w3, torch.float32, device)
             L.pack_x3(self.flat_w, self.flat_w3)             # (every trainable tensor's rows are whole 32-element groups, f9 aside: it has its own pack)
             mirror = self.flat_w3
         else:
             mirror = self.flat_w
         # transposed (dgrad) packs [IC][T][OC]: ONE flat buffer, ONE launch over all layers (same offsets as flat_w)
-        if (getattr(self, "flat_wt", None) is None or self.flat_wt.dtype != tdt or self.flat_wt.device != device
-                or self.flat_wt.numel() != self.flat_w.numel()):
-            self.flat_wt = torch.empty(self.flat_w.numel(), device=device, dtype=tdt)
+        wt = self._flat_like(self.flat_wt, tdt, device)
+        if wt is not self.flat_wt:
+            self.flat_wt = wt
             rows, tiles = [], 0
             for b in arch.BLOCKS:
                 if b[0] in arch.FROZEN_BLOCKS:
@@ -291,8 +364,8 @@ class Engine:
             self._wt_table64 = torch.tensor(rows64, dtype=torch.int64, device=device)
             self._wt_tiles64 = t64
         self._wt_pending = (dt, mirror)
-        if dt == L.F32X3 and (getattr(self, "flat_wt3", None) is None or self.flat_wt3.numel() != self.flat_w.numel() or self.flat_wt3.device != device):
-            self.flat_wt3 = torch.empty_like(self.flat_w)
+        if dt == L.F32X3:
+            self.flat_wt3 = self._flat_like(self.flat_wt3, torch.float32, device)
         for b in arch.BLOCKS:
             if b[0] in arch.FROZEN_BLOCKS:
                 continue
@@ -307,7 +380,7 @@ class Engine:
             # then neither written nor re-read (444 MB each way for b7).  b6 / b7: [W_branch1 | W_branch2b2]; b5 (the residual-block form, 3x3 last conv +
             # 1x1 skip conv at stride 1): [W_branch2b1 (9 taps) | W_branch1].  All pieces are copied from the bf16 mirror in ONE launch into buffers
             # that persist across steps (`_fused_plan`).
-            if dt == L.BF16 and FUSE_SKIP:
+            if dt == L.BF16:
                 plan = self._fused_plan(device)
                 for nm, buf in plan["fwd_bufs"].items():
                     P["w"][nm + ".skip_fused"] = buf
@@ -320,7 +393,7 @@ class Engine:
                     P["w"][nm] = mirror[off:off + n].view(co, 1, ci)
                 return
             # fused head: rows [fc_proj | fc8 | 0]; its transposed pack is made from the two f32 masters directly
-            hb = getattr(self, "_head_bufs", None)               # persistent: the zero padding (rows / columns 149..191) is written once
+            hb = self._head_bufs                                 # persistent: the zero padding (rows / columns 149..191) is written once
             if hb is None or hb[0] != (dt, str(device)):
                 # (the forward pack holds 256 rows — 107 of them zero: the head GEMM then runs on the 256-tile kernel, which reads whole 256-row weight
                 #  tiles and masks the columns >= HEAD_LD; conv_igemm w_rows)
@@ -363,20 +436,17 @@ class Engine:
         return P
 
     def _join_late_packs(self, device):
-        ev = getattr(self, "_late_ev", None)
-        if ev is not None:
-            torch.cuda.current_stream(device).wait_event(ev)
+        if self._late_ev is not None:
+            torch.cuda.current_stream(device).wait_event(self._late_ev)
             self._late_ev = None
 
     def finish_packs(self):
         """The transposed (dgrad) packs [IC][T][OC] of the current weights: ONE launch over all layers into the flat buffer the
         `P["wt"]` views point into, plus the K-concatenated backward packs of the two-source launches.  Runs on the CURRENT
         stream (the fused step calls it on a side stream and joins before the backward pass); no-op when already done."""
-        pend = getattr(self, "_wt_pending", None)
-        if pend is None:
+        if self._wt_pending is None:
             return
-        self._wt_pending = None
-        dt, mirror = pend
+        (dt, mirror), self._wt_pending = self._wt_pending, None
         P = self.packs
         if dt == L.BF16:                                     # from the bf16 mirror (written by the fused SGD): a third of the traffic
             L.pack_transposed_batch_bf16(mirror, self.flat_wt, self._wt_table64, self._wt_table64.shape[0], self._wt_tiles64)
@@ -407,7 +477,7 @@ class Engine:
 
     def _fused_plan(self, device):
         """Persistent K-concatenated pack buffers + the piece tables of wseg_copy2d_batch (16-byte = 8-element units), built once per device."""
-        plan = getattr(self, "_fused", None)
+        plan = self._fused
         if plan is not None and plan["device"] == device:
             return plan
 
@@ -490,28 +560,11 @@ class Engine:
         V = len(xs)
         dev = xs[0].device
         dt = DT_OF[net.precision]
-        tdt = L.TORCH_DTYPE[dt]
         P = self.ensure_packs(dev, dt)
         N = xs[0].shape[0]
         masks = S["masks"] if S is not None else None
-
-        def rows_of(dims):
-            return sum(N * h * w for (h, w) in dims)
-
-        def offs_of(dims):
-            o, out = 0, []
-            for (h, w) in dims:
-                out.append(o)
-                o += N * h * w
-            return out
-
-        def E(m, c):
-            return torch.empty((m, c), device=dev, dtype=tdt)
-
-        def conv(inp, wname, out, out2, cin, cout, k, stride, dil, din, dout, **kw):
-            seg2 = (din[1][0], din[1][1], dout[1][0], dout[1][1]) if V == 2 else None
-            L.conv_igemm(inp, P["w"][wname], out, out2, N=N, IH=din[0][0], IW=din[0][1], IC=cin, OH=dout[0][0], OW=dout[0][1],
-                         OC=cout, KH=k, KW=k, stride=stride, dil=dil, pad=dil * (k // 2), seg2=seg2, dtype=_cdt(dt), **kw)
+        ps = _Pass(N, dev, dt, P)
+        E, conv, rows_of = ps.E, ps.conv, ps.rows_of
 
         def next_bn(i):
             if i + 1 < len(arch.BLOCKS):
@@ -524,7 +577,7 @@ class Engine:
             dims = [(x.shape[2], x.shape[3]) for x in xs]
             sc, sh = P["bn"]["b2.bn_branch2a"]
             t = E(rows_of(dims), 64)
-            for x, off, (H, W) in zip(xs, offs_of(dims), dims):
+            for x, off, (H, W) in zip(xs, ps.offs_of(dims), dims):
                 L.stem_conv_kc(x, P["w"]["conv1a_kc"], sc, sh, None, t[off:], N, H, W, L.F32 if dt == L.F32X3 else dt)
             xraw = None
         else:
@@ -537,25 +590,26 @@ class Engine:
                 self._join_late_packs(dev)
             (nsc, nsh), ndrop = next_bn(i)
             nxt_same = i + 1 < len(arch.BLOCKS) and arch.block_same_shape(arch.BLOCKS[i + 1])
-            k0 = 3 if kind == "res" else 1
-            odims = [(_out_size(h, k0, stride, fd if kind == "res" else 1), _out_size(w, k0, stride, fd if kind == "res" else 1)) for (h, w) in dims]
+            odims = arch.block_out_dims(b, dims)
             Mo = rows_of(odims)
+            skip = Conv(name + ".conv_branch1", cin, cout, 1, stride, 1, dims, odims)
             if kind == "res":
                 s1, sh1 = P["bn"][name + ".bn_branch2b1"]
                 v = E(Mo, mid)
-                conv(t, name + ".conv_branch2a", None, v, cin, mid, 3, stride, fd, dims, odims, scale=s1, shift=sh1)
+                conv(Conv(name + ".conv_branch2a", cin, mid, 3, stride, fd, dims, odims), t, None, v, scale=s1, shift=sh1)
                 xn = E(Mo, cout) if nxt_same else None
                 tn = final_t if (final_t is not None and i == last - 1) else E(Mo, cout)
-                assert tn.shape == (Mo, cout) and tn.dtype == tdt
+                assert tn.shape == (Mo, cout) and tn.dtype == L.TORCH_DTYPE[dt]
+                c2b1 = Conv(name + ".conv_branch2b1", mid, cout, 3, 1, d, odims, odims)
                 if (name + ".skip_fused") in P["w"]:            # last conv + 1x1 skip conv as one two-source launch
-                    conv(v, name + ".skip_fused", xn, tn, mid, cout, 3, 1, d, odims, odims, in2=t, IC2=cin, scale=nsc, shift=nsh, drop=ndrop)
+                    conv(c2b1._replace(name=name + ".skip_fused"), v, xn, tn, in2=t, IC2=cin, scale=nsc, shift=nsh, drop=ndrop)
                 else:
                     if same:
                         rpost = xraw
                     else:
                         rpost = E(Mo, cout)
-                        conv(t, name + ".conv_branch1", rpost, None, cin, cout, 1, stride, 1, dims, odims)
-                    conv(v, name + ".conv_branch2b1", xn, tn, mid, cout, 3, 1, d, odims, odims, r_post=rpost, scale=nsc, shift=nsh, drop=ndrop)
+                        conv(skip, t, rpost)
+                    conv(c2b1, v, xn, tn, r_post=rpost, scale=nsc, shift=nsh, drop=ndrop)
                 if save:
                     S[name] = dict(t=t, v=v)
             else:
@@ -565,17 +619,17 @@ class Engine:
                 d1 = masks[name + ".dropout_2b1"] if masks else None
                 d2 = masks[name + ".dropout_2b2"] if masks else None
                 v1 = E(Mo, c4)
-                conv(t, name + ".conv_branch2a", None, v1, cin, c4, 1, stride, 1, dims, odims, scale=s1, shift=sh1, drop=d1)
+                conv(Conv(name + ".conv_branch2a", cin, c4, 1, stride, 1, dims, odims), t, None, v1, scale=s1, shift=sh1, drop=d1)
                 v2 = E(Mo, c2)
-                conv(v1, name + ".conv_branch2b1", None, v2, c4, c2, 3, 1, d, odims, odims, scale=s2, shift=sh2, drop=d2)
+                conv(Conv(name + ".conv_branch2b1", c4, c2, 3, 1, d, odims, odims), v1, None, v2, scale=s2, shift=sh2, drop=d2)
                 xn = None
                 tn = E(Mo, cout)
                 if (name + ".skip_fused") in P["w"]:            # out = [t | v2] . [W_branch1 | W_branch2b2]^T in one launch
-                    conv(t, name + ".skip_fused", xn, tn, cin, cout, 1, 1, 1, odims, odims, in2=v2, scale=nsc, shift=nsh, drop=ndrop)
+                    conv(Conv(name + ".skip_fused", cin, cout, 1, 1, 1, odims, odims), t, xn, tn, in2=v2, scale=nsc, shift=nsh, drop=ndrop)
                 else:
                     b1 = E(Mo, cout)
-                    conv(t, name + ".conv_branch1", b1, None, cin, cout, 1, stride, 1, dims, odims)
-                    conv(v2, name + ".conv_branch2b2", xn, tn, c2, cout, 1, 1, 1, odims, odims, r_post=b1, scale=nsc, shift=nsh, drop=ndrop)
+                    conv(skip, t, b1)
+                    conv(Conv(name + ".conv_branch2b2", c2, cout, 1, 1, 1, odims, odims), v2, xn, tn, r_post=b1, scale=nsc, shift=nsh, drop=ndrop)
                 if save:
                     S[name] = dict(t=t, v1=v1, v2=v2)
             sdims[name] = (dims, odims)
@@ -594,9 +648,7 @@ class Engine:
         N = xs[0].shape[0]
         dims = [tuple(x.shape[2:]) for x in xs]
         for b in arch.BLOCKS[:arch.N_FROZEN_BLOCKS]:
-            name, kind, cin, mid, cout, stride, fd, d, p = b
-            k0 = 3 if kind == "res" else 1
-            dims = [(_out_size(h, k0, stride, fd if kind == "res" else 1), _out_size(w, k0, stride, fd if kind == "res" else 1)) for (h, w) in dims]
+            dims = arch.block_out_dims(b, dims)
         return sum(N * h * w for (h, w) in dims), arch.BLOCKS[arch.N_FROZEN_BLOCKS - 1][4]
 
     def run_prefix(self, xs, out=None):
@@ -606,6 +658,13 @@ class Engine:
         out: a [prefix_out_shape] tensor for the result — the fused step allocates it on the CALLER's stream, so that the one tensor that crosses from the
         prefix stream to the next step belongs to the caller's allocator pool (no record_stream bookkeeping: with it the reserved memory grew by 6 GB)."""
         return self._run_blocks(xs, None, 0, arch.N_FROZEN_BLOCKS, False, None, final_t=out)
+
+    def run_backbone(self, xs):
+        """conv1a and every block, no head (the AffinityNet puts its own on top).  Returns (state, pass): state["t"] = relu(bn7(conv6)),
+        state["conv4"] / ["conv5"] the inputs of b5 / b6, state["dims"] the stride-8 dims; `pass.conv` launches on the current packs."""
+        st = self._run_blocks(xs, None, 0, len(arch.BLOCKS), False, None)
+        self._join_late_packs(xs[0].device)
+        return st, _Pass(st["N"], xs[0].device, st["dt"], self.packs)
 
     def run_forward(self, xs, save, lowres=False, prefix=None):
         """xs: list of one or two image batches (same N).  Two views are BATCHED: every activation is one row
@@ -617,7 +676,6 @@ class Engine:
         assert V in (1, 2)
         dev = xs[0].device
         dt = DT_OF[net.precision]
-        tdt = L.TORCH_DTYPE[dt]
         P = self.ensure_packs(dev, dt)
         N = xs[0].shape[0]
         assert all(x.shape[0] == N for x in xs)
@@ -630,34 +688,21 @@ class Engine:
         S["dims"].update(prefix["sdims"])
         st = self._run_blocks(xs, prefix, arch.N_FROZEN_BLOCKS, len(arch.BLOCKS), save, S)
         t, dims, conv4, conv5 = st["t"], st["dims"], st["conv4"], st["conv5"]
+        ps = _Pass(N, dev, dt, P)
+        E, conv = ps.E, ps.conv
 
-        def rows_of(dims):
-            return sum(N * h * w for (h, w) in dims)
-
-        def offs_of(dims):
-            o, out = 0, []
-            for (h, w) in dims:
-                out.append(o)
-                o += N * h * w
-            return out
-
-        def E(m, c):
-            return torch.empty((m, c), device=dev, dtype=tdt)
-
-        def conv(inp, wname, out, out2, cin, cout, k, stride, dil, din, dout, **kw):
-            seg2 = (din[1][0], din[1][1], dout[1][0], dout[1][1]) if V == 2 else None
-            L.conv_igemm(inp, P["w"][wname], out, out2, N=N, IH=din[0][0], IW=din[0][1], IC=cin, OH=dout[0][0], OW=dout[0][1],
-                         OC=cout, KH=k, KW=k, stride=stride, dil=dil, pad=dil * (k // 2), seg2=seg2, dtype=_cdt(dt), **kw)
+        def head_conv(nm, cin, cout):                         # the heads are 1x1 convs on the stride-8 maps
+            return Conv(nm, cin, cout, 1, 1, 1, dims, dims)
 
         fea = t                                               # relu(bn7(x)) * dropout7   [M,4096]
         self._join_late_packs(dev)
-        M = rows_of(dims)
-        offs = offs_of(dims)
+        M = ps.rows_of(dims)
+        offs = ps.offs_of(dims)
         head = E(M, HEAD_LD)
-        conv(fea, "head", head, None, 4096, HEAD_LD, 1, 1, 1, dims, dims, relu_lt=128, w_rows=256)
+        conv(head_conv("head", 4096, HEAD_LD), fea, head, relu_lt=128, w_rows=256)
         feat = E(M, FEAT_LD)
-        conv(conv4, "f8_3", feat, None, 512, 64, 1, 1, 1, dims, dims, epi=2, ld_out=FEAT_LD)
-        conv(conv5, "f8_4", feat.view(-1)[64:], None, 1024, 128, 1, 1, 1, dims, dims, epi=2, ld_out=FEAT_LD)
+        conv(head_conv("f8_3", 512, 64), conv4, feat, epi=2, ld_out=FEAT_LD)
+        conv(head_conv("f8_4", 1024, 128), conv5, feat.view(-1)[64:], epi=2, ld_out=FEAT_LD)
         G = torch.empty(M, 32, device=dev, dtype=torch.float32)
         views = []
         for x, off, (h, w) in zip(xs, offs, dims):
@@ -669,7 +714,7 @@ class Engine:
             L.pcm_xs(x, feat[off:], FEAT_LD, 192, FEAT_LD, N, x.shape[2], x.shape[3], h, w)
             views.append(dict(h=h, w=w, H=x.shape[2], W=x.shape[3], off=off, rows=N * hw, cam_low=cam_low))
         Fm = E(M, 192)
-        conv(feat, "f9", Fm, None, FEAT_LD, 192, 1, 1, 1, dims, dims)
+        conv(head_conv("f9", FEAT_LD, 192), feat, Fm)
         Fh = torch.empty(M, 192, device=dev, dtype=torch.float32)
         nrm = torch.empty(M, device=dev, dtype=torch.float32)
         L.l2norm_forward(Fm, 192, Fh, nrm, M)
@@ -720,36 +765,21 @@ class Engine:
         self.finish_packs()                                  # (no-op when the caller already made the transposed packs)
         P = self.packs
         dt = S["dt"]
-        tdt = L.TORCH_DTYPE[dt]
-        N, V, M = S["N"], S["V"], S["M"]
+        N, M = S["N"], S["M"]
         hdims = S["hdims"]
         dev = S["fea"].device
         masks = S["masks"]
         self.attach_grads()
-
-        def E(m, c):
-            return torch.empty((m, c), device=dev, dtype=tdt)
-
-        def rows_of(dims):
-            return sum(N * h * w for (h, w) in dims)
+        ps = _Pass(N, dev, dt, P)
+        E, rows_of = ps.E, ps.rows_of
 
         def trainable(nm):
             return self.conv_param(nm).requires_grad
 
-        def seg(din, dout):
-            return (din[1][0], din[1][1], dout[1][0], dout[1][1]) if V == 2 else None
+        def head_conv(nm, cin, cout):
+            return Conv(nm, cin, cout, 1, 1, 1, hdims, hdims)
 
-        # Weight gradients only feed flat_g: with WSEG_WGRAD_STREAM=1 they run on a second HIP stream so that the
-        # partially filled last round of a dgrad launch (1 workgroup / CU kernels) is back-filled by wgrad
-        # workgroups and vice versa.  Operands are kept alive until the streams join.
         main = torch.cuda.current_stream(dev)
-        wstream = None
-        if os.environ.get("WSEG_WGRAD_STREAM", "0") == "1":
-            wstream = getattr(self, "_wgrad_stream", None)
-            if wstream is None or wstream.device != dev:
-                wstream = self._wgrad_stream = torch.cuda.Stream(dev)
-            wstream.wait_stream(main)
-        keep = []
         pcm_join = [None]                                    # the PCM branch's stream until main has waited for it
 
         planes = {}                                          # split-bf16 mode: (hi, lo) bf16 planes of an f32 operand, made once per tensor
@@ -762,64 +792,40 @@ class Engine:
                 planes[key] = (hi, lo, t_)                   # (keeps the source alive: the key is its address)
             return planes[key][:2]
 
-        def wgrad_launch(x, dy, dw, big_x3, **args):
-            if big_x3:
+        def wgrad(c, x, dy, **kw):
+            """dW of conv `c` accumulated into its slice of flat_g (nothing when the parameter is frozen)"""
+            if not trainable(c.name):
+                return
+            dw = self.grad_slice(c.name)
+            args = dict(c.wgrad_kw(N), dtype=_cdt(dt), **kw)
+            if dt == L.F32X3 and c.cin >= 256 and c.cout >= 256 and not kw and x.is_contiguous() and dy.is_contiguous() \
+                    and x.shape[1] == c.cin and dy.shape[1] == c.cout:
                 # split-bf16 products on the bf16 pixel-reduction kernel: dW += X_lo^T dY_hi + X_hi^T dY_lo + X_hi^T dY_hi (it accumulates
                 # with float atomics anyway) — 3 launches at the bf16 kernel's rate beat one launch of the f32-tile kernel that splits inside
                 (xh, xl), (dh, dl) = split(x), split(dy)
-                args = dict(args, dtype=None)
+                args["dtype"] = None
                 L.conv_wgrad(xl, dh, dw, **args)
                 L.conv_wgrad(xh, dl, dw, **args)
                 L.conv_wgrad(xh, dh, dw, **args)
             else:
                 L.conv_wgrad(x, dy, dw, **args)
 
-        def wgrad(nm, x, dy, cin, cout, k, stride, dil, din, dout, **kw):
-            if trainable(nm):
-                off, n = self.offsets[nm]
-                args = dict(N=N, IH=din[0][0], IW=din[0][1], IC=cin, OH=dout[0][0], OW=dout[0][1],
-                            OC=cout, KH=k, KW=k, stride=stride, dil=dil, pad=dil * (k // 2), seg2=seg(din, dout), dtype=_cdt(dt), **kw)
-                big_x3 = dt == L.F32X3 and cin >= 256 and cout >= 256 and not kw and x.is_contiguous() and dy.is_contiguous() \
-                    and x.shape[1] == cin and dy.shape[1] == cout
-                if wstream is None:
-                    wgrad_launch(x, dy, self.flat_g[off:off + n], big_x3, **args)
-                else:
-                    keep.append((x, dy))
-                    wstream.wait_event(torch.cuda.current_stream(dev).record_event())      # (main, or the PCM branch's stream)
-                    with torch.cuda.stream(wstream):
-                        wgrad_launch(x, dy, self.flat_g[off:off + n], big_x3, **args)
-
         def block_done(nm):
-            """All weight gradients of block `nm` are enqueued: the data-parallel trainer may start reducing its bucket.  With a
-            separate wgrad stream the collective (issued behind `main`) must first wait for the kernels on that stream."""
+            """All weight gradients of block `nm` are enqueued: the data-parallel trainer may start reducing its bucket."""
             if self.block_done_hook is not None:
-                if wstream is not None:
-                    main.wait_event(wstream.record_event())
                 if pcm_join[0] is not None:                  # the last bucket (b7 + heads) holds the PCM branch's f9 / f8_3 / f8_4 gradients
                     main.wait_stream(pcm_join[0])
                     pcm_join[0] = None
                 self.block_done_hook(nm)
 
-        def pair_args(pair):
-            """`pair_wgrad` of L.conv_igemm for the weight gradient (name, x, dy, cin, cout, k, stride, dil, din, dout), or None (then the caller
-            launches it on its own): bf16 mode, no separate weight-gradient stream"""
-            if pair is None:
-                return None
-            pnm, px, pdy, pcin, pcout, pk, pstride, pdil, pdin, pdout = pair
-            if not (dt == L.BF16 and wstream is None and trainable(pnm)):
-                return None
-            off, n = self.offsets[pnm]
-            return (px, pdy, self.flat_g[off:off + n],
-                    dict(N=N, IH=pdin[0][0], IW=pdin[0][1], IC=pcin, OH=pdout[0][0], OW=pdout[0][1], OC=pcout, KH=pk, KW=pk, stride=pstride,
-                         dil=pdil, pad=pdil * (pk // 2), seg2=seg(pdin, pdout), dtype=_cdt(dt)))
-
-        def dgrad(dy, wname, out, conv_cin, conv_cout, k, stride, dil, din, dout, pair=None, **kw):
-            # in = dY over the conv's OUTPUT dims (dout), out = dX over its INPUT dims (din)
-            # pair = (name, x, dy, cin, cout, k, stride, dil, din, dout): a weight gradient of the same dY, launched in the same grid (bf16 mode)
-            seg2 = (dout[1][0], dout[1][1], din[1][0], din[1][1]) if V == 2 else None
-            pw = pair_args(pair)
-            L.conv_igemm(dy, P["wt"][wname], out, None, N=N, IH=dout[0][0], IW=dout[0][1], IC=conv_cout, OH=din[0][0], OW=din[0][1],
-                         OC=conv_cin, KH=k, KW=k, stride=stride, dil=dil, pad=dil * (k // 2), mode=1, seg2=seg2, dtype=_cdt(dt), pair_wgrad=pw, **kw)
+        def dgrad(c, dy, out, pair=None, **kw):
+            """dX of conv `c`.  pair = (conv, x, dy): a weight gradient of the same dY, launched in the same grid in bf16 mode
+            (wseg_conv_bwd_pair) and on its own behind this launch otherwise."""
+            pw = None
+            if pair is not None and dt == L.BF16 and trainable(pair[0].name):
+                pc, px, pdy = pair
+                pw = (px, pdy, self.grad_slice(pc.name), dict(pc.wgrad_kw(N), dtype=_cdt(dt)))
+            L.conv_igemm(dy, P["wt"][c.name], out, None, dtype=_cdt(dt), pair_wgrad=pw, **c.dgrad_kw(N), **kw)
             if pair is not None and pw is None:
                 wgrad(*pair)
 
@@ -845,15 +851,13 @@ class Engine:
             d_rvd.append(dr)
         # ---- PCM branch -> f9, f8_3, f8_4.  It ends in WEIGHT gradients only (f8_3 / f8_4 read conv4 / conv5 detached, resnet38_contrast.py:63-64),
         # so nothing of the backbone's backward pass waits for it: it runs on its own stream beside the first blocks (0.5 ms of small kernels + two PCM
-        # launches that otherwise sit in front of the head's data gradient), joined before the gradients are consumed (WSEG_PCM_STREAM=0: in line).
+        # launches that otherwise sit in front of the head's data gradient), joined before the gradients are consumed
+        # (same-box A/B against running it in line: 35.25 / 35.16 -> 34.94 / 34.94 ms per step; the b7 launches it overlaps slow down by ~1 %).
         pcm_stream = None
         if any(d is not None for d in d_rvd):
-            if os.environ.get("WSEG_PCM_STREAM", "1") != "0":   # (same-box A/B: 35.25 / 35.16 -> 34.94 / 34.94 ms per step; the b7 launches it overlaps slow down by ~1 %)
-                pcm_stream = getattr(self, "_pcm_stream", None)
-                if pcm_stream is None or pcm_stream.device != dev:
-                    pcm_stream = self._pcm_stream = torch.cuda.Stream(dev)
-                pcm_stream.wait_stream(main)
-            with torch.cuda.stream(pcm_stream if pcm_stream is not None else main):
+            pcm_stream = self.stream("pcm", dev)
+            pcm_stream.wait_stream(main)
+            with torch.cuda.stream(pcm_stream):
                 DN = torch.empty(M, 32, device=dev, dtype=torch.float32)
                 dFh = torch.zeros(M, 192, device=dev, dtype=torch.float32)
                 DNb = torch.empty(M, 32, device=dev, dtype=torch.bfloat16) if S["Fb"] is not None else None
@@ -869,17 +873,14 @@ class Engine:
                         L.pcm_backward(S["Fh"][off:], S["G"][off:], dr.contiguous(), vw["rvd"], vw["den"], DN[off:], dFh[off:], N, hw)
                 dF = E(M, 192)
                 L.l2norm_backward(S["Fm"], 192, dFh, S["nrm"], dF, 192, M)
-                if trainable("f9"):
-                    # feature rows are [f8_3 64 | f8_4 128 | x_s 3 | pad], f9.weight's columns [x_s | f8_3 | f8_4]: the weight-gradient kernel rotates
-                    # its dW columns by 3 and accumulates straight into the flat gradient buffer (no staging tensor, no slice adds)
-                    off9, n9 = self.offsets["f9"]
-                    L.conv_wgrad(S["feat"], dF, self.flat_g[off9:off9 + n9], N=N, IH=hdims[0][0], IW=hdims[0][1], IC=FEAT_LD, OH=hdims[0][0],
-                                 OW=hdims[0][1], OC=192, KH=1, KW=1, IC_dw=195, seg2=seg(hdims, hdims), dtype=_cdt(dt), dw_rot=3)
+                # feature rows are [f8_3 64 | f8_4 128 | x_s 3 | pad], f9.weight's columns [x_s | f8_3 | f8_4]: the weight-gradient kernel rotates
+                # its dW columns by 3 and accumulates straight into the flat gradient buffer (no staging tensor, no slice adds)
+                wgrad(head_conv("f9", FEAT_LD, 192), S["feat"], dF, IC_dw=195, dw_rot=3)
                 if trainable("f8_3") or trainable("f8_4"):
                     d_feat = E(M, FEAT_LD)
-                    dgrad(dF, "f9", d_feat, FEAT_LD, 192, 1, 1, 1, hdims, hdims, epi=1, mask=S["feat"])
-                    wgrad("f8_3", S["conv4"], d_feat, 512, 64, 1, 1, 1, hdims, hdims, ld_dy=FEAT_LD)
-                    wgrad("f8_4", S["conv5"], d_feat.view(-1)[64:], 1024, 128, 1, 1, 1, hdims, hdims, ld_dy=FEAT_LD)
+                    dgrad(head_conv("f9", FEAT_LD, 192), dF, d_feat, epi=1, mask=S["feat"])
+                    wgrad(head_conv("f8_3", 512, 64), S["conv4"], d_feat, ld_dy=FEAT_LD)
+                    wgrad(head_conv("f8_4", 1024, 128), S["conv5"], d_feat.view(-1)[64:], ld_dy=FEAT_LD)
         pcm_join[0] = pcm_stream
         # ---- head
         if d_head_rows is None:
@@ -892,14 +893,12 @@ class Engine:
                 off, hw = vw["off"], vw["h"] * vw["w"]
                 gf = g[2].contiguous().float() if g[2] is not None else None
                 L.head_grad_rows(gf, dc.contiguous() if dc is not None else None, S["head"][off:], d_head_rows[off:], HEAD_LD, N, hw)
-        if trainable("fc_proj") or trainable("fc8"):
-            off, _ = self.offsets["fc_proj"]
-            L.conv_wgrad(S["fea"], d_head_rows, self.flat_g[off:off + 149 * 4096], N=N, IH=hdims[0][0], IW=hdims[0][1], IC=4096,
-                         OH=hdims[0][0], OW=hdims[0][1], OC=HEAD_LD, KH=1, KW=1, OC_dw=149, seg2=seg(hdims, hdims), dtype=_cdt(dt))
+        chead = head_conv("head", 4096, HEAD_LD)
+        if trainable("fc_proj") or trainable("fc8"):          # fc_proj and fc8 are adjacent in flat_g: one [149,4096] block
+            L.conv_wgrad(S["fea"], d_head_rows, self.grad_slice("fc_proj", 149 * 4096), OC_dw=149, dtype=_cdt(dt), **chead.wgrad_kw(N))
         s7, _ = P["bn"]["bn7"]
         D = E(M, 4096)
-        dgrad(d_head_rows, "head", D, 4096, HEAD_LD, 1, 1, 1, hdims, hdims, epi=1, scale=s7,
-              drop=masks["dropout7"] if masks else None, mask=S["fea"])
+        dgrad(chead, d_head_rows, D, epi=1, scale=s7, drop=masks["dropout7"] if masks else None, mask=S["fea"])
         # ---- blocks, last to first trainable
         for i in range(len(arch.BLOCKS) - 1, -1, -1):
             b = arch.BLOCKS[i]
@@ -913,34 +912,31 @@ class Engine:
             sv = S[name]
             sa, _ = P["bn"][name + ".bn_branch2a"]
             first_trainable = name == "b3"               # its input comes from the frozen prefix
+            c1 = Conv(name + ".conv_branch1", cin, cout, 1, stride, 1, din, dout)
             if kind == "res":
                 s1, _ = P["bn"][name + ".bn_branch2b1"]
+                c2a = Conv(name + ".conv_branch2a", cin, mid, 3, stride, fd, din, dout)
+                c2b1 = Conv(name + ".conv_branch2b1", mid, cout, 3, 1, d, dout, dout)
                 du = E(Mo, mid)
                 # (each data gradient takes the weight gradient of the same dY into its launch: wseg_conv_bwd_pair)
-                dgrad(D, name + ".conv_branch2b1", du, mid, cout, 3, 1, d, dout, dout, epi=1, scale=s1, mask=sv["v"],
-                      pair=(name + ".conv_branch2b1", sv["v"], D, mid, cout, 3, 1, d, dout, dout))
-                pair2a = (name + ".conv_branch2a", sv["t"], du, cin, mid, 3, stride, fd, din, dout)
-                if not (same and not first_trainable):
-                    wgrad(*pair2a)
-                pair1 = (name + ".conv_branch1", sv["t"], D, cin, cout, 1, stride, 1, din, dout)
+                dgrad(c2b1, D, du, epi=1, scale=s1, mask=sv["v"], pair=(c2b1, sv["v"], D))
                 fused_skip = (name + ".skip_fused") in P["wt"] and not first_trainable
-                if not same and not (fused_skip and pair_args(pair1) is not None):
-                    wgrad(*pair1)
+                if not (same and not first_trainable):
+                    wgrad(c2a, sv["t"], du)
+                if not same and not fused_skip:
+                    wgrad(c1, sv["t"], D)
                 if first_trainable:
                     block_done(name)
                     break
                 Din = E(Mi, cin)
                 if same:
-                    dgrad(du, name + ".conv_branch2a", Din, cin, mid, 3, stride, fd, din, dout, epi=1, scale=sa, mask=sv["t"], r_post=D, pair=pair2a)
-                elif (name + ".skip_fused") in P["wt"]:        # both data gradients into t: 9 taps of du + one K segment of D
-                    seg2 = (dout[1][0], dout[1][1], din[1][0], din[1][1]) if V == 2 else None
-                    L.conv_igemm(du, P["wt"][name + ".skip_fused"], Din, None, N=N, IH=dout[0][0], IW=dout[0][1], IC=mid, OH=din[0][0], OW=din[0][1],
-                                 OC=cin, KH=3, KW=3, stride=1, dil=fd, pad=fd, mode=1, in2=D, IC2=cout, epi=1, scale=sa, mask=sv["t"], seg2=seg2,
-                                 pair_wgrad=pair_args(pair1))        # (+ the skip conv's weight gradient: same D)
+                    dgrad(c2a, du, Din, epi=1, scale=sa, mask=sv["t"], r_post=D, pair=(c2a, sv["t"], du))
+                elif fused_skip:                               # both data gradients into t: 9 taps of du + one K segment of D (+ the skip conv's weight gradient: same D)
+                    dgrad(c2a._replace(name=name + ".skip_fused"), du, Din, in2=D, IC2=cout, epi=1, scale=sa, mask=sv["t"], pair=(c1, sv["t"], D))
                 else:
                     tmp = E(Mi, cin)
-                    dgrad(D, name + ".conv_branch1", tmp, cin, cout, 1, stride, 1, din, dout)
-                    dgrad(du, name + ".conv_branch2a", Din, cin, mid, 3, stride, fd, din, dout, epi=1, scale=sa, mask=sv["t"], r_pre=tmp)
+                    dgrad(c1, D, tmp)
+                    dgrad(c2a, du, Din, epi=1, scale=sa, mask=sv["t"], r_pre=tmp)
                 D = Din
                 block_done(name)
             else:
@@ -949,30 +945,27 @@ class Engine:
                 s2, _ = P["bn"][name + ".bn_branch2b2"]
                 d1 = masks[name + ".dropout_2b1"] if masks else None
                 d2 = masks[name + ".dropout_2b2"] if masks else None
+                c2a = Conv(name + ".conv_branch2a", cin, c4, 1, stride, 1, din, dout)
+                c2b1 = Conv(name + ".conv_branch2b1", c4, c2, 3, 1, d, dout, dout)
+                c2b2 = Conv(name + ".conv_branch2b2", c2, cout, 1, 1, 1, dout, dout)
                 du2 = E(Mo, c2)
-                dgrad(D, name + ".conv_branch2b2", du2, c2, cout, 1, 1, 1, dout, dout, epi=1, scale=s2, drop=d2, mask=sv["v2"],
-                      pair=(name + ".conv_branch2b2", sv["v2"], D, c2, cout, 1, 1, 1, dout, dout))
+                dgrad(c2b2, D, du2, epi=1, scale=s2, drop=d2, mask=sv["v2"], pair=(c2b2, sv["v2"], D))
                 du1 = E(Mo, c4)
-                dgrad(du2, name + ".conv_branch2b1", du1, c4, c2, 3, 1, d, dout, dout, epi=1, scale=s1, drop=d1, mask=sv["v1"],
-                      pair=(name + ".conv_branch2b1", sv["v1"], du2, c4, c2, 3, 1, d, dout, dout))
-                wgrad(name + ".conv_branch2a", sv["t"], du1, cin, c4, 1, stride, 1, din, dout)
+                dgrad(c2b1, du2, du1, epi=1, scale=s1, drop=d1, mask=sv["v1"], pair=(c2b1, sv["v1"], du2))
+                wgrad(c2a, sv["t"], du1)
                 Din = E(Mi, cin)
                 if (name + ".skip_fused") in P["wt"]:          # both 1x1 data gradients into t as ONE two-source product (+ the skip conv's weight gradient)
-                    dgrad(D, name + ".skip_fused", Din, cin, cout, 1, 1, 1, din, dout, epi=1, scale=sa, mask=sv["t"], in2=du1, IC2=c4,
-                          pair=(name + ".conv_branch1", sv["t"], D, cin, cout, 1, stride, 1, din, dout))
+                    dgrad(Conv(name + ".skip_fused", cin, cout, 1, 1, 1, din, dout), D, Din, epi=1, scale=sa, mask=sv["t"], in2=du1, IC2=c4,
+                          pair=(c1, sv["t"], D))
                 else:
                     tmp = E(Mi, cin)
-                    dgrad(D, name + ".conv_branch1", tmp, cin, cout, 1, stride, 1, din, dout,
-                          pair=(name + ".conv_branch1", sv["t"], D, cin, cout, 1, stride, 1, din, dout))
-                    dgrad(du1, name + ".conv_branch2a", Din, cin, c4, 1, stride, 1, din, dout, epi=1, scale=sa, mask=sv["t"], r_pre=tmp)
+                    dgrad(c1, D, tmp, pair=(c1, sv["t"], D))
+                    dgrad(c2a, du1, Din, epi=1, scale=sa, mask=sv["t"], r_pre=tmp)
                 D = Din
                 block_done(name)
         planes.clear()
         if pcm_join[0] is not None:
             main.wait_stream(pcm_join[0])
-        if wstream is not None:
-            main.wait_stream(wstream)
-            keep.clear()
 
 
 class _NetFunction(torch.autograd.Function):

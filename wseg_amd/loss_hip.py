@@ -17,32 +17,9 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
-from .engine import HEAD_LD
+from .engine import DT_OF, HEAD_LD
 
 _TIE_CACHE = {}
-
-
-def _side_streams(eng, dev):
-    st = getattr(eng, "_side_streams", None)
-    if st is None or st[0].device != dev:
-        st = eng._side_streams = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
-    return st
-
-
-def _prefix_stream(eng, dev):
-    """Stream of the next batch's frozen prefix (step(lookahead=...)).  An ordinary stream: a high-priority or CU-masked one
-    (hipExtStreamCreateWithCUMask, to keep a few CUs free for the loss kernels) slowed EVERY conv launch of the step (36.1 -> 45-49 ms)."""
-    st = getattr(eng, "_prefix_stream", None)
-    if st is None or st.device != dev:
-        st = eng._prefix_stream = torch.cuda.Stream(dev)
-    return st
-
-
-def _aux_stream(eng, dev):
-    st = getattr(eng, "_aux_stream", None)
-    if st is None or st.device != dev:
-        st = eng._aux_stream = torch.cuda.Stream(dev)
-    return st
 
 
 def cpu_tie_pattern(P, k, device=None):
@@ -199,24 +176,24 @@ def step(model, img1, img2, label20, bg_threshold=0.20, rng=None, rng_parity=Fal
     label20 = label20.to(dev).float().contiguous()
     eng.ensure_flat(dev)
     eng.attach_grads()
-    defer = os.environ.get("WSEG_DEFER_PACKS", "1") != "0"      # (0: A/B switch — packs and memset before the forward pass)
-    from .engine import DT_OF
-    use_streams = os.environ.get("WSEG_STREAMS", "1") != "0"
-    eng.ensure_packs(dev, DT_OF[model.precision], defer_wt=defer, late_stream=_aux_stream(eng, dev) if (defer and use_streams) else None)
-    if zero_grads and not defer:
-        eng.flat_g.zero_()
+    # Streams (Engine.stream, created in this order on the first step): aux — weight packs and the gradient memset; side0 / side1 — the
+    # per-view map losses; prefix — the next batch's frozen prefix.  The prefix stream is an ordinary one: a high-priority or CU-masked
+    # stream (hipExtStreamCreateWithCUMask, to keep a few CUs free for the loss kernels) slowed EVERY conv launch of the step
+    # (36.1 -> 45-49 ms).
+    aux = eng.stream("aux", dev)
+    eng.ensure_packs(dev, DT_OF[model.precision], defer_wt=True, late_stream=aux)
     acc = torch.zeros(8, device=dev, dtype=torch.float32)   # [cls1+cls2, (rvmin1+rvmin2)/2, er_sum, ecr, cross, cross2, intra]
     # The two views are independent until ER/ECR: run each on its own HIP stream so the small 128x128 view's
     # launches (which cannot fill 256 CUs) overlap with the 448x448 view's.
     main = torch.cuda.current_stream(dev)
-    side = _side_streams(eng, dev) if use_streams else (main, main)
+    side = (eng.stream("side0", dev), eng.stream("side1", dev))
     # Both views go through the network in ONE batched pass (two row segments per launch); the per-view map
     # losses then run on their own HIP streams.
     outs, ctx = eng.run_forward([img1, img2], save=True, lowres=True, prefix=prefix)
     fork = main.record_event()
     pst = None
     if lookahead is not None:
-        pst = _prefix_stream(eng, dev)
+        pst = eng.stream("prefix", dev)
         n1 = lookahead["img1"]
         # the two tensors that cross from the prefix stream into the next step are allocated HERE, on the caller's stream (its allocator pool: they are
         # written on the prefix stream, which the caller waits for before its backward pass, and freed in the caller's program order)
@@ -229,11 +206,10 @@ def step(model, img1, img2, label20, bg_threshold=0.20, rng=None, rng_parity=Fal
             lookahead["img2"], lookahead["prefix"] = n2, eng.run_prefix([n1, n2], out=t_next)
     # Backward-only preparation — the transposed weight packs (420 MB of traffic) and the gradient memset (420 MB) — on a third
     # stream behind the forward pass: it runs while the loss phase's small kernels leave the chip's bandwidth idle.
-    aux = _aux_stream(eng, dev) if use_streams else main
     aux.wait_event(fork)
     with torch.cuda.stream(aux):
         eng.finish_packs()
-        if zero_grads and defer:
+        if zero_grads:
             eng.flat_g.zero_()
     P = N * 256
     tie_idx = (bg_topk_idx.to(device=dev, dtype=torch.int32) if bg_topk_idx is not None else cpu_tie_pattern(P, 32, dev))
@@ -292,10 +268,10 @@ def step(model, img1, img2, label20, bg_threshold=0.20, rng=None, rng_parity=Fal
     # ---- pixel-to-prototype similarities + hard-pixel records (main stream, concurrently with the ER / ECR chain)
     # (the radix-select kernel is also the faster one on a single rank — 47 vs 118 us; the sort-based kernel remains the
     #  RNG-parity path, which replays the reference's host random stream)
-    global_intra = distributed or (not rng_parity and os.environ.get("WSEG_INTRA_GLOBAL", "1") == "1")
+    global_intra = distributed or not rng_parity
     rank = dist.get_rank() if distributed else 0
     # record pass (similarities that only RANK pixels): exact-f32 MFMA in fp32 mode, split-bf16 products in the bf16 / bf16x3 modes
-    nce_x3 = model.precision != "fp32" and os.environ.get("WSEG_NCE_X3", "1") != "0"
+    nce_x3 = model.precision != "fp32"
     # ONE launch for both views: per-pixel records {label, similarity to the pixel's own-class prototype, random key} straight from
     # the raw features (csrc/loss.hip nce_records): the inputs of the hard-pixel sampling.  Over the GLOBAL batch under data
     # parallelism (the reference samples on the gathered batch): the records (96 KB per rank for both views) are
@@ -306,10 +282,10 @@ def step(model, img1, img2, label20, bg_threshold=0.20, rng=None, rng_parity=Fal
         v.rkey = _random_keys(P, rank, vi, dev) if global_intra else None
     L.nce_records([dict(F=v.F, p_own=v.protos, y_own=v.y, rkey=v.rkey, rec=rec[vi]) for vi, v in enumerate(views)], P, split_bf16=nce_x3)
     grec = rec
-    if global_intra and distributed:                        # (collectives stay on the main stream, in program order)
+    if distributed:                                         # (collectives stay on the main stream, in program order)
         grec = _f32(world, 2, 3, P, dev=dev)
         dist.all_gather_into_tensor(grec.view(world * 6, P), rec.view(6, P))
-    elif rng_parity and not global_intra:
+    elif not global_intra:
         for vi, v in enumerate(views):                     # view 1 fully before view 2 (RNG order of the reference)
             v.w_intra = _f32(P, dev=dev)
             L.intra_weights(v.y, rec[vi, 1], None, _rand_flags(v.y, rng, P), v.w_intra, P, ld_s=1)
@@ -318,9 +294,6 @@ def step(model, img1, img2, label20, bg_threshold=0.20, rng=None, rng_parity=Fal
         if global_intra:
             v.w_intra = _f32(P, dev=dev)
             L.intra_weights_global(grec.view(-1)[vi * 3 * P:], v.w_intra, P, world, rank, float(world), 6 * P)
-        elif not rng_parity:
-            v.w_intra = _f32(P, dev=dev)
-            L.intra_weights(v.y, rec[vi, 1], torch.rand(P, device=dev), None, v.w_intra, P, ld_s=1)
 
     fork2 = main.record_event()
     weights_of(0, v1)

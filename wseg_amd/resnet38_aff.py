@@ -105,29 +105,22 @@ class Net(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("wseg_amd.resnet38_aff runs only on an MI355X (HIP) device; there is no CPU fallback")
         x = x.contiguous().float()
-        eng = self._engine.active(x.device)
-        dt = engine.DT_OF[self.precision]
-        tdt = L.TORCH_DTYPE[dt]
-        eng.ensure_packs(x.device, dt)
-        st = eng._run_blocks([x], None, 0, len(arch.BLOCKS), False, None)       # conv4 / conv5 / conv6 (resnet38d.py:160-189)
-        eng._join_late_packs(x.device)
-        P = eng.packs
+        st, ps = self._engine.active(x.device).run_backbone([x])       # conv4 / conv5 / conv6 (resnet38d.py:160-189)
         N = x.shape[0]
-        (h, w), = st["dims"]
+        dims = st["dims"]
+        (h, w), = dims
         r = pair_radius(h, w, self.radius)
         M = N * h * w
-        cdt = engine._cdt(dt)
 
-        def conv(inp, name, out, cin, cout, ld_out):
-            L.conv_igemm(inp, P["w"][name], out, None, N=N, IH=h, IW=w, IC=cin, OH=h, OW=w, OC=cout, KH=1, KW=1,
-                         epi=3, ld_out=ld_out, dtype=cdt)
+        def conv(inp, name, out, cin, cout):                  # 1x1 conv + ELU into a column slice of `out`
+            ps.conv(engine.Conv(name, cin, cout, 1, 1, 1, dims, dims), inp, out, epi=3, ld_out=FEAT_C)
 
-        feat = torch.empty(M, FEAT_C, device=x.device, dtype=tdt)
-        conv(st["conv4"], "f8_3", feat, 512, 64, FEAT_C)
-        conv(st["conv5"], "f8_4", feat.view(-1)[64:], 1024, 128, FEAT_C)
-        conv(st["t"], "f8_5", feat.view(-1)[192:], 4096, 256, FEAT_C)
-        f9 = torch.empty(M, FEAT_C, device=x.device, dtype=tdt)
-        conv(feat, "f9", f9, FEAT_C, FEAT_C, FEAT_C)
+        feat = ps.E(M, FEAT_C)
+        conv(st["conv4"], "f8_3", feat, 512, 64)
+        conv(st["conv5"], "f8_4", feat.view(-1)[64:], 1024, 128)
+        conv(st["t"], "f8_5", feat.view(-1)[192:], 4096, 256)
+        f9 = ps.E(M, FEAT_C)
+        conv(feat, "f9", f9, FEAT_C, FEAT_C)
         n_from = (h - r + 1) * (w - 2 * r + 2)
         aff = torch.empty(N, L.aff_num_offsets(r), n_from, device=x.device, dtype=torch.float32)
         L.aff_pairs(f9, FEAT_C, FEAT_C, aff, N, h, w, r)

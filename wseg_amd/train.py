@@ -44,7 +44,9 @@ class Trainer:
         self.bg_topk_idx = bg_topk_idx
         self.world, self.distributed = dist_state()
         self._pending = []
-        if self.distributed and os.environ.get("WSEG_BUCKETS", "1") != "0":   # (one joint backward)
+        self._buckets = None
+        self._lookahead = None
+        if self.distributed:
             # Gradient all-reduce overlapped with backward: the flat gradient buffer completes back to front, so each
             # bucket (b7 + heads, b5..b6, b4*, b3*: 154 / 143 / 109 / 13 MB) is reduced as soon as its last weight
             # gradient is enqueued — RCCL runs on its own stream behind those kernels while dgrad/wgrad continue.
@@ -52,11 +54,10 @@ class Trainer:
 
     def _on_block_done(self, name):
         eng = self.model._engine
-        buckets = getattr(self, "_buckets", None)
-        if buckets is None:
-            buckets = self._buckets = eng.grad_buckets()
-        if name in buckets:
-            lo, hi = buckets[name]
+        if self._buckets is None:
+            self._buckets = eng.grad_buckets()
+        if name in self._buckets:
+            lo, hi = self._buckets[name]
             self._pending.append(dist.all_reduce(eng.flat_g[lo:hi], async_op=True))
 
     def step(self, img1, label20, next_img1=None):
@@ -67,7 +68,7 @@ class Trainer:
             raise RuntimeError("Trainer.step needs GPU tensors (no CPU fallback)")
         from . import loss_hip
         img1 = img1.contiguous().float()
-        pre, self._lookahead = getattr(self, "_lookahead", None), None
+        pre, self._lookahead = self._lookahead, None
         # the prefix is reused only for the SAME image tensor AND the same frozen weights / BN buffers / precision it was computed from
         # (a load_state_dict or a BN-buffer edit between the two calls changes Engine.frozen_key: the stale activations are dropped)
         if (pre is not None and pre["img1"].data_ptr() == img1.data_ptr() and pre["img1"].shape == img1.shape and pre["version"] == img1._version
@@ -76,7 +77,7 @@ class Trainer:
         else:
             img2, prefix = second_view(img1), None
         la = None
-        if next_img1 is not None and os.environ.get("WSEG_PREFETCH", "1") != "0":
+        if next_img1 is not None:
             n1 = next_img1.contiguous().float()
             if n1.is_cuda and n1.shape == img1.shape:
                 la = {"img1": n1, "version": n1._version}
@@ -96,7 +97,7 @@ class Trainer:
                 for work in self._pending:
                     work.wait()
                 self._pending = []
-            else:
+            else:                                           # (no bucket hook installed: a caller that drives the backward pass itself)
                 dist.all_reduce(model._engine.flat_g)       # RCCL over xGMI; averaged by grad_scale below
             opt.wseg_grad_scale = 1.0 / self.world
         opt.step()
