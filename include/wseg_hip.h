@@ -362,6 +362,44 @@ int wseg_rw_pool(const float* cams, const int* src, float bg, float* pooled, int
  * cropped to [H][W] (aff_infer.py:110-139): pred uint8 [H][W].  planes <= 32. */
 int wseg_rw_finish(const float* cam_rw, unsigned char* pred, int planes, int dh, int dw, int H, int W, void* stream);
 
+/* ---- fully connected CRF, mean field with exact Gaussian kernels (contrast_infer.py:102-134 --out_crf, aff_prepare.py:34-50) ----------
+ * The reference calls pydensecrf, whose filters are a permutohedral-lattice approximation; these entry points evaluate every pair
+ * (DESIGN.md §3 "crf" states the update).  One image of N = H*W pixels (pixel i = y*W + x), M labels, S label sets sharing the image.
+ * Buffers of the all-pairs filter, npad = wseg_crf_padded_pixels(N) (N rounded up to WSEG_CRF_PIX_ALIGN), NC = wseg_crf_columns(S, M):
+ *   feat [npad/4][8][4]  f32   pixel quad, feature (x, y, r, g, b, 0, 0, 0) as integers, slot i & 3
+ *   Qn   [npad/4][NC][4] f32   pixel quad, column s*M + c, slot i & 3: n_i * Q, zero for i >= N and in the unused columns
+ *   out  [npad][NC]      f32   sum_j k(f_i, f_j) * Qn[j][column] (rows i >= N hold finite values nobody reads)
+ * All pointers are device pointers the caller allocated; nothing is allocated or synchronised inside. */
+#define WSEG_CRF_PIX_ALIGN 128
+#define WSEG_CRF_MAX_LABELS 32
+#define WSEG_CRF_MAX_COLUMNS 64     /* S * M rounded up to 16 (21 labels: S <= 3) */
+#define WSEG_CRF_MAX_RADIUS 128     /* window radius ceil(6.5 * sxy) of the separable Gaussian (sxy <= 19.6) */
+#define WSEG_CRF_BG_CONST 0
+#define WSEG_CRF_BG_POWER 1
+int wseg_crf_padded_pixels(int npix);
+int wseg_crf_columns(int S, int n_labels);
+/* labels[i] = argmax_c T[c][i], the first maximum winning: T[c] = cams[src[c]] for src[c] >= 0 (else 0), c = 1..n_labels-1;
+ * T[0] = param (rule WSEG_CRF_BG_CONST) or (1 - max_c T[c][i])^param with T[0] = 0 inside the max (rule WSEG_CRF_BG_POWER).
+ * cams: [ncams][npix] f32 device; src: n_labels host ints (src[0] ignored). */
+int wseg_crf_labels(const float* cams, const int* src, int n_labels, int rule, float param, unsigned char* labels, int npix, void* stream);
+/* img uint8 [H][W][3] -> feat, the unit column `ones` ([npad/4][16][4]: column 0 = 1 for i < N) the normalisation pass filters, and the
+ * Gaussian's ng[i] = 1/sqrt(sum_j k + 1e-20) over its window. */
+int wseg_crf_prepare(const unsigned char* img, int H, int W, float gauss_sxy, float* feat, float* ones, float* ng, void* stream);
+/* the hot path: out = K . Qn over ALL pairs, K[i][j] = exp(-((dx^2+dy^2)/sxy^2 + (dr^2+dg^2+db^2)/srgb^2)/2); k in f32 on the VALU from
+ * exact integer differences, the product on v_mfma_f32_16x16x4_f32 (exact f32 accumulation).  ncols = NC (16, 32, 48 or 64). */
+int wseg_crf_bilateral(const float* feat, const float* Qn, float* out, int npix, int ncols, float sxy, float srgb, void* stream);
+/* n[i] = 1/sqrt(sums[i*stride] + 1e-20): the bilateral n from column 0 of wseg_crf_bilateral(feat, ones, ...) (stride 16) */
+int wseg_crf_rsqrt(const float* sums, int stride, float* n, int npix, void* stream);
+/* out[p][y][x] = sum over the window of exp(-(dx^2+dy^2)/(2 sxy^2)) * in[p][y+dy][x+dx], two 1-D passes through tmp (same size) */
+int wseg_crf_gaussian(const float* in, float* tmp, float* out, int planes, int H, int W, float sxy, void* stream);
+/* one mean-field update for S label sets (labels uint8 [S][npix]): logit[c] = -U[c] + w_gaussian * ng[i]*outg[s*M+c][i] +
+ * w_bilateral * nb[i]*outb[i][s*M+c] with U[c] = -ln(gt_prob) at c == label, -ln((1-gt_prob)/(M-1)) elsewhere; Q = softmax(logit).
+ * outb == outg == NULL: the initial Q = softmax(-U).  Writes the next filter inputs Qn (= nb*Q, layout above) and Qg (= ng*Q,
+ * [S*M][npix]) and, where non-NULL, Qout / logits ([S][M][npix] f32) and amax (uint8 [S][npix], the first maximum). */
+int wseg_crf_update(const unsigned char* labels, const float* outb, const float* outg, const float* nb, const float* ng, float* Qn,
+                    float* Qg, float* Qout, float* logits, unsigned char* amax, int S, int n_labels, int npix, float gt_prob,
+                    float w_bilateral, float w_gaussian, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -402,3 +402,22 @@ def rw_pool(cams, src, bg, pooled, H, W, dh, dw):
     """src: 21 ints, plane c <- cams[src[c]] (-1: zero plane; plane 0 is the bg score)."""
     _call("wseg_rw_pool", _v(cams), (C.c_int * 21)(*[int(s) for s in src]), _f(bg), _v(pooled), H, W, dh, dw)
 def rw_finish(cam_rw, pred, planes, dh, dw, H, W): _call("wseg_rw_finish", _v(cam_rw), _v(pred), planes, dh, dw, H, W)
+
+
+# ---------------------------------------------------------------------------------------------- dense CRF, exact mean field (csrc/crf.hip)
+CRF_PIX_ALIGN, CRF_MAX_LABELS, CRF_MAX_COLUMNS = 128, 32, 64     # WSEG_CRF_*
+CRF_BG_CONST, CRF_BG_POWER = 0, 1
+
+
+def crf_padded_pixels(npix): return int(lib.wseg_crf_padded_pixels(int(npix)))
+def crf_columns(S, n_labels): return int(lib.wseg_crf_columns(int(S), int(n_labels)))
+def crf_labels(cams, src, n_labels, rule, param, labels, npix):
+    """src: n_labels ints, plane c <- cams[src[c]] (-1: zero plane; plane 0 follows the background rule)."""
+    _call("wseg_crf_labels", _v(cams), (C.c_int * n_labels)(*[int(s) for s in src]), n_labels, int(rule), _f(param), _v(labels), npix)
+def crf_prepare(img, H, W, gauss_sxy, feat, ones, ng): _call("wseg_crf_prepare", _v(img), H, W, _f(gauss_sxy), _v(feat), _v(ones), _v(ng))
+def crf_bilateral(feat, Qn, out, npix, ncols, sxy, srgb): _call("wseg_crf_bilateral", _v(feat), _v(Qn), _v(out), npix, ncols, _f(sxy), _f(srgb))
+def crf_rsqrt(sums, stride, n, npix): _call("wseg_crf_rsqrt", _v(sums), stride, _v(n), npix)
+def crf_gaussian(inp, tmp, out, planes, H, W, sxy): _call("wseg_crf_gaussian", _v(inp), _v(tmp), _v(out), planes, H, W, _f(sxy))
+def crf_update(labels, outb, outg, nb, ng, Qn, Qg, Qout, logits, amax, S, n_labels, npix, gt_prob, w_bilateral, w_gaussian):
+    _call("wseg_crf_update", _v(labels), _v(outb), _v(outg), _v(nb), _v(ng), _v(Qn), _v(Qg), _v(Qout), _v(logits), _v(amax), S, n_labels, npix,
+          _f(gt_prob), _f(w_bilateral), _f(w_gaussian))

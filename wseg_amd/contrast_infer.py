@@ -1,7 +1,9 @@
 """CLI of the reference's contrast_infer.py (same flags, :19-31) on the MI355X path.  Writes the same files:
 <out_cam>/<name>.npy (pickled dict class -> float32[H,W] of the present classes, :82-90) and
-<out_cam_pred>/<name>.png (uint8 argmax, :97-99).  --out_crf is accepted and rejected: dense CRF needs
-pydensecrf (absent offline, CPU-only post-process, out of the hot path)."""
+<out_cam_pred>/<name>.png (uint8 argmax, :97-99), and <out_crf>/<name>.png (:102-134): the uint8 arg-max of the dense CRF on the CAM
+labels with a constant background score of 0.26, sxy 50 / srgb 5, 10 iterations.  Two quirks of the reference are kept: the CRF's
+background score is the constant 0.26 whatever --out_cam_pred_alpha says, and --crf_iters is parsed and never used (t = 10).  The CRF is wseg_amd.crf: exact mean field on the device; agreement with pydensecrf's permutohedral
+approximation is unmeasured."""
 import argparse
 import importlib
 import os
@@ -12,10 +14,20 @@ import torch
 
 from . import data as wdata
 from . import synth
+from .crf import crf_inference, labels_from_cams
 from .infer import infer_image
 
+CRF_BG_SCORE, CRF_BILATERAL, CRF_GAUSSIAN, CRF_T = 0.26, (50, 5, 10), (3, 3), 10        # contrast_infer.py:104, 121-122, 113
 
-def main(argv=None):
+
+def crf_prediction(img_u8, cam_dict):
+    """contrast_infer.py:104-112 `_crf`: uint8 [H, W] device arg-max of the CRF on the labels of [0.26] ++ cam_dict"""
+    labels = labels_from_cams(cam_dict, bg_score=CRF_BG_SCORE, size=tuple(img_u8.shape[:2]), device=img_u8.device)
+    _, amax = crf_inference(img_u8, labels, t=CRF_T, bilateral=CRF_BILATERAL, gaussian=CRF_GAUSSIAN, return_argmax=True)
+    return amax[0]
+
+
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("--weights", required=True, type=str)
     parser.add_argument("--network", default="wseg_amd.resnet38_contrast", type=str)
@@ -29,9 +41,11 @@ def main(argv=None):
     parser.add_argument("--crf_iters", default=10, type=float)
     parser.add_argument("--labels", default="voc12/cls_labels.npy", type=str)
     parser.add_argument("--precision", default=None, choices=[None, "bf16", "fp32", "bf16x3"])
-    args = parser.parse_args(argv)
-    if args.out_crf is not None:
-        raise SystemExit("--out_crf needs pydensecrf, which is not available offline (out of the accelerated path)")
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
 
     Net = getattr(importlib.import_module(args.network), 'Net')
     model = Net(precision=args.precision) if args.precision else Net()
@@ -48,9 +62,13 @@ def main(argv=None):
     # One image behind: the device work of image i is enqueued (nothing in infer_image synchronises), its outputs start their way to pinned host
     # buffers, and only then are the files of image i - 1 written — the png / npy writes and the loader hand-over overlap the GPU instead of
     # alternating with it (the reference's loop, contrast_infer.py:52-99, syncs per image on `.cpu()`).
-    def start(img_name, pred, cam_dict):
+    def start(img_name, pred, cam_dict, crf_pred):
         host_pred = torch.empty(pred.shape, dtype=pred.dtype, pin_memory=True)
         host_pred.copy_(pred, non_blocking=True)
+        host_crf = None
+        if crf_pred is not None:
+            host_crf = torch.empty(crf_pred.shape, dtype=crf_pred.dtype, pin_memory=True)
+            host_crf.copy_(crf_pred, non_blocking=True)
         host_cams = None
         if args.out_cam is not None:
             host_cams = {}
@@ -60,17 +78,19 @@ def main(argv=None):
                 host_cams[k] = h
         ev = torch.cuda.Event()
         ev.record()
-        return img_name, host_pred, host_cams, ev
+        return img_name, host_pred, host_cams, host_crf, ev
 
     def finish(item):
-        img_name, host_pred, host_cams, ev = item
+        img_name, host_pred, host_cams, host_crf, ev = item
         ev.synchronize()
+        if host_crf is not None:
+            PIL.Image.fromarray(host_crf.numpy()).save(os.path.join(args.out_crf, img_name + '.png'))
         if host_cams is not None:
             np.save(os.path.join(args.out_cam, img_name + '.npy'), {k: v.numpy() for k, v in host_cams.items()})
         if args.out_cam_pred is not None:
             PIL.Image.fromarray(host_pred.numpy()).save(os.path.join(args.out_cam_pred, img_name + '.png'))
 
-    for d in (args.out_cam, args.out_cam_pred):
+    for d in (args.out_cam, args.out_cam_pred, args.out_crf):
         if d is not None:
             os.makedirs(d, exist_ok=True)
     pending = None
@@ -78,8 +98,12 @@ def main(argv=None):
         img_name, label = img_name[0], label[0]
         with PIL.Image.open(wdata.get_img_path(img_name, args.voc12_root)) as im:      # (header only: the reference decodes the image again for its shape)
             W, H = im.size
+            rgb = np.array(im.convert("RGB")) if args.out_crf is not None else None
         norm_cam, pred, cam_dict = infer_image(model, img_list, label, (H, W), args.out_cam_pred_alpha)
-        item = start(img_name, pred, cam_dict)
+        crf_pred = None
+        if rgb is not None:
+            crf_pred = crf_prediction(torch.from_numpy(rgb).pin_memory().to(pred.device, non_blocking=True), cam_dict)
+        item = start(img_name, pred, cam_dict, crf_pred)
         if pending is not None:
             finish(pending)
         pending = item

@@ -144,3 +144,20 @@ def synthetic_cam_dict(H, W, classes, seed=0, device="cpu"):
         m = m + 0.05 * _uniform(f"camtex{c}", seed, (H, W), 0.0, 1.0, device)
         out[int(c)] = (m / m.max()).to(torch.float32)
     return out
+
+
+def synthetic_rgb_image(H, W, seed=0):
+    """uint8 [H, W, 3] (CPU): a piecewise-smooth picture — four flat-coloured ellipses (centres / colours from the hash, semi-axes
+    0.35 H x 0.35 W, later ones on top) over black, a horizontal ramp of 20 levels and +-12 levels of hash texture.  N(0, 1) noise
+    (synthetic_images) makes a bilateral kernel degenerate: no two pixels are alike.  float64 arithmetic, rounded half to even."""
+    u = hash_uniform(1234 + seed, H * W * 3).double().reshape(H, W, 3)
+    r = hash_uniform(99 + seed, 40).double()
+    yy = torch.arange(H, dtype=torch.float64).view(H, 1)
+    xx = torch.arange(W, dtype=torch.float64).view(1, W)
+    img = torch.zeros(H, W, 3, dtype=torch.float64)
+    for k in range(4):
+        cy, cx = r[5 * k] * H, r[5 * k + 1] * W
+        inside = ((yy - cy) / (0.35 * H)) ** 2 + ((xx - cx) / (0.35 * W)) ** 2 < 1
+        img[inside] = r[5 * k + 2:5 * k + 5] * 255
+    img += (20 * xx / W).unsqueeze(-1) + 24 * (u - 0.5)
+    return img.round().clamp_(0, 255).to(torch.uint8)
