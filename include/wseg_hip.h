@@ -72,8 +72,8 @@ typedef struct wseg_conv_desc {
   int32_t relu_lt;     /* epi 0: ReLU on `out` channels < relu_lt (fused head: f_proj | cam); 0 = none */
   int32_t bm_hint;     /* 0 = library chooses the tile (64 / 128 pixel rows x 128 channels, or the 256 x 256 phase-pipelined
                           bf16 kernel for large layers with OC % 256 == 0, or the 512 x 128 one for OC = 128 layers with many pixels);
-                          64 / 128 / 224 / 256 = force; 259 = test hook (512 x 128 tile); negative values: development
-                          probes, refused unless the library was built with -DWSEG_PROBES */
+                          64 / 128 / 224 / 256 = force; 259 = test hook (512 x 128 tile).  A forced 224 / 256 / 259 whose shape the kernel
+                          does not take (see wseg_conv_plan) runs on the 64 / 128-row tiles: wseg_conv_plan tells which */
   /* optional SECOND row segment (the 128x128 view batched behind the 448x448 view in one launch): rows
    * [0, N*OH*OW) use (IH,IW,OH,OW); rows beyond use (IH2,IW2,OH2,OW2), same N, their input pixels follow the
    * first segment's N*IH*IW rows; drop then has 2N rows.  OH2 == 0: single segment. */
@@ -82,7 +82,8 @@ typedef struct wseg_conv_desc {
    * a residual block's last conv and its 1x1 skip conv (network/resnet38d.py:35-47, 83-97: branch1 + branch2) as ONE product: the
    * second source is one extra K segment read at the output pixel itself, so the skip output is neither written nor re-read.  With
    * the transposed packs and mode 1 the same form is the sum of the two data gradients into the block's input.  Same-size stride-1
-   * convolution (pad = dil*(KH/2)), bf16, OC % 256 == 0, IC2 % 64 == 0 (0: IC2 = IC), in2 on the OUTPUT pixel grid; NULL: none. */
+   * convolution (pad = dil*(KH/2)), bf16, OC % 256 == 0, IC2 % 64 == 0 (0: IC2 = IC), epi 0..2 (the form exists on the 256-tile kernel only,
+   * which has no ELU: epi 3 is refused), in2 on the OUTPUT pixel grid; NULL: none. */
   const void* in2;
   int32_t ld_in2, IC2;
   int32_t w_rows;      /* rows the weight pack really holds (>= OC; 0 = OC).  A pack zero-padded to a multiple of 256 rows lets a launch whose OC is
@@ -111,12 +112,40 @@ typedef struct wseg_wgrad_desc {
                                   dw_rot = 3 writes f9's gradient in the parameter's own column order (128-tile kernel only; 0 = none) */
 } wseg_wgrad_desc;
 int wseg_conv_wgrad(const wseg_wgrad_desc* d, void* stream);
+
+/* ---- what a launch would run ---------------------------------------------------------------
+ * The plan of wseg_conv_igemm / wseg_conv_wgrad for a descriptor: the same validation (same status, same wseg_last_error text) and the same
+ * choice, made by the function the launch itself calls.  Pure host arithmetic: no data pointer is dereferenced and no device is touched, so
+ * any non-NULL pointer values do. */
+#define WSEG_CONV_64x128 1          /* conv_igemm_kernel, 64-row tiles (any dtype, any epilogue) */
+#define WSEG_CONV_128x128 2         /* conv_igemm_kernel, 128-row tiles */
+#define WSEG_CONV_224x256 3         /* conv_igemm256_kernel with 224-row tiles (NI = 7); takes what WSEG_CONV_256x256 takes */
+#define WSEG_CONV_256x256 4         /* conv_igemm256_kernel with 256-row tiles (NI = 8): bf16 / split-bf16, epi 0..2, OC % 256 == 0 or a pack padded to it (w_rows) */
+#define WSEG_CONV_512x128 5         /* conv_igemm512x128_kernel: bf16, epi 0..2, OC % 128 == 0, forward or stride-1 data gradient */
+#define WSEG_WGRAD_128x128 6        /* conv_wgrad_kernel (any dtype) */
+#define WSEG_WGRAD_256x256 7        /* conv_wgrad_pipe_kernel: bf16, IC and OC >= 256 */
+typedef struct wseg_launch_plan {
+  int32_t family;                   /* WSEG_CONV_* / WSEG_WGRAD_* */
+  int32_t tile_rows, tile_cols;     /* conv: pixel rows x output channels; wgrad: dw rows (oc) x columns (ic) */
+  int32_t nwg;                      /* workgroups of the stand-alone launch */
+  int32_t perm;                     /* conv: stride-2 data gradient walking its rows in parity-class order */
+  int32_t tapf;                     /* conv, 256-tile kernel: the fast tap arithmetic (32-bit offsets, no per-tap division) */
+  int32_t nsplit;                   /* wgrad: pixel ranges the reduction is split over */
+  int32_t unit;                     /* wgrad, pipe kernel: its UNIT variant (same-size stride-1 layers) */
+} wseg_launch_plan;
+int wseg_conv_plan(const wseg_conv_desc* d, wseg_launch_plan* out);
+int wseg_wgrad_plan(const wseg_wgrad_desc* d, wseg_launch_plan* out);
+
 /* A layer's data gradient (`dg`: mode 1) and a weight gradient (`wg`) as ONE launch: both depend only on dY (autograd runs them back to back:
  * network/resnet38d.py:17-44 backward), and as one grid the weight-gradient tiles back-fill the data gradient's partly filled last round and the two
- * kinds of tile do not end — and store — at the same time.  Qualifies: bf16, stride-1 single-source data gradient on the 256-tile kernel + a
- * weight gradient on the 256 x 256 phase-pipelined kernel; anything else runs as the two ordinary launches, in that order.  Same results. */
+ * kinds of tile do not end — and store — at the same time.  Qualifies: a bf16 stride-1 data gradient (one or two sources, `out` only, no bm_hint) whose plan is the 256-tile kernel
+ * with tapf, + a weight gradient whose plan is the 256 x 256 phase-pipelined kernel; anything else runs as the two ordinary launches, in that order.
+ * Same results.  Both descriptors are validated before anything is launched: a bad `wg` launches nothing, also where the pair would have run
+ * as two launches.  WSEG_BWD_PAIR=0 in the environment: never one grid (scripts/profile_layers.py, scripts/check_pair_equivalence.py). */
 int wseg_conv_bwd_pair(const wseg_conv_desc* dg, const wseg_wgrad_desc* wg, void* stream);
-int wseg_conv_bwd_pair_fuses(const wseg_conv_desc* dg, const wseg_wgrad_desc* wg);   /* 1: one grid, 0: two launches, < 0: bad arguments (launches nothing) */
+/* the plan of wseg_conv_bwd_pair: 1 = one grid of ((dg_plan.nwg + 7) & ~7) + wg_plan.nwg workgroups, 0 = two launches, < 0 = a bad descriptor
+ * (launches nothing); both plans are filled as wseg_conv_plan / wseg_wgrad_plan fill them */
+int wseg_conv_bwd_pair_plan(const wseg_conv_desc* dg, const wseg_wgrad_desc* wg, wseg_launch_plan* dg_plan, wseg_launch_plan* wg_plan);
 
 /* ---- weight packing ----------------------------------------------------------------------
  * master f32 [OC][T][IC] -> fwd pack [OCp][T][ICp] and transposed pack [ICp][T][OCp] in `dtype`
@@ -165,7 +194,6 @@ int wseg_head_split(const void* head, int ld, int c0, float* cam_low, float* cma
 int wseg_cam_gate(const float* cam_low, const float* cmax, float* G, int N, int hw, void* stream);
 int wseg_pcm_xs(const float* x_nchw, void* feat, int ld, int c_xs, int c_end, int N, int H, int W, int h, int w, int dtype, void* stream);
 int wseg_head_grad_rows(const float* d_fproj, const float* d_cam_low, const void* head, void* d_head, int ld, int N, int hw, int dtype, void* stream);
-int wseg_planar_to_rows(const float* planar, void* rows, int ld, int c0, int C, int N, int hw, int dtype, void* stream);
 
 /* planar bilinear resize of [planes][ih][iw] f32 (F.interpolate(mode='bilinear'), align_corners
  * 0/1 — resnet38_contrast.py:57-59, contrast_train.py:131-134,145-152,180; contrast_infer.py:62).
@@ -207,10 +235,7 @@ int wseg_pcm_backward_bf16(const void* Fb, const void* Gb, const void* Gl, const
  * scalars accumulated with atomicAdd (caller zeroes them).
  *  plane_stats        per (n,c): {max relu(U), min relu(U), sum U, argmax, argmin, 0}      (:142, visualization.py:62-66)
  *  cls_loss           mean BCE-with-logits of the GAP logits (:159-160) + its per-pixel gradient as a plane bias
- *  rvmin_values       q = max_{c>=1} U*L and its arg channel (:19-21)
  *  select_kth         k-th order statistic per row by 4-pass radix select + strict sums (torch.topk(...)[0].sum(), :22, :170-171)
- *  rvmin_backward     gradient of adaptive_min_pooling_loss into dU
- *  norm_resize_*      L * bilinear_{S->OS}(max_norm(U)) and its backward incl. the max/min routes (:145-158)
  *  er_ecr_prep        ER sum + gradients, bg = 1-max fg, max_onehot, signed ECR differences (:163-169)
  *  ecr_backward       gradient of the top-K mean (:170-171)
  *  rows_resize_forward  f_proj rows -> [N*oh*ow][128] f32, bilinear align_corners=True (:179)
@@ -228,12 +253,13 @@ int wseg_plane_stats(const float* U, float* stats, long planes, int npix, void* 
  * reference's upsampled [N,21,S,S] tensors (resnet38_contrast.py:57-59, 540 MB per view) and their gradients are
  * never materialised; U(y,x) = bilinear(low, align_corners=True) is recomputed by one pinned expression.
  *  up_plane_stats          = plane_stats(U)                      (contrast_train.py:142,155; visualization.py:62-67)
- *  up_rvmin_values         = rvmin_values(U_rv)                  (:16-22)
- *  up_norm_resize_forward  = norm_resize_forward(U)              (:145-158)
+ *  up_rvmin_values         q = max_{c>=1} U_rv*L and its arg channel per pixel (:16-22)
+ *  up_norm_resize_forward  L * bilinear_{S->OS}(max_norm(U))    (:145-158)
  *  resize_adjoint_ones     wvec[y] = sum over the S upsampled rows of their weight on low-res row y (the GAP gradient)
  *  up_maps_backward        d_low[pl] = all gradients of plane pl: max_norm + resize backward of G (NULL: none) with the
  *                          max/min routes, plane_bias[pl]*wvec_y*wvec_x (NULL: none), and the min-pool selection
- *                          (q/argc/res of select_kth, NULL: none; k, coef as in rvmin_backward). */
+ *                          (q/argc/res of select_kth, NULL: none; the pixels among the k smallest q of an image with q > 0
+ *                          send coef * label to their arg channel). */
 int wseg_up_plane_stats(const float* low, float* stats, long planes, int h, int w, int S, const float* label20 /* nullable: all planes; else only bg + labelled classes of [N][20] */, void* workspace, void* stream);
 int wseg_up_rvmin_values(const float* low, const float* label20, float* q, unsigned char* argc, int N, int h, int w, int S, void* stream);
 int wseg_up_norm_resize_forward(const float* low, const float* stats, const float* label20, float* out, int N, int h, int w, int S, int OS, void* stream);
@@ -242,16 +268,12 @@ int wseg_up_maps_backward(const float* G, const float* low, const float* stats, 
                           const float* wvec_y, const float* wvec_x, const float* q, const unsigned char* argc, const float* res,
                           int k, float coef, float* d_low, int N, int h, int w, int S, int OS, void* stream);
 int wseg_cls_loss(const float* stats, const float* label20, float* loss_out, float* plane_bias, int N, int npix, float coef, void* stream);
-int wseg_rvmin_values(const float* U, const float* label20, float* q, unsigned char* argc, int N, int npix, void* stream);
 size_t wseg_select_workspace_bytes(int rows);
 int wseg_select_kth(const float* vals, int rows, int n, int k, int largest, int use_abs, int relu_vals, float* res, void* workspace, void* stream);
 int wseg_select_finish(const float* res, int rows, int k, int relu_vals, float scale, float* loss_out, void* stream);
 /* the 8 logged scalars (contrast_train.py:174, 389-395, 401-408) from the step's accumulators acc = [cls1+cls2, (rvmin1+rvmin2)/2, er_sum, ecr, cross,
  * cross2, intra, -]:  out8 = [loss, loss_cls, loss_er, loss_ecr, loss_nce, loss_intra_nce, loss_cross_nce, loss_cross_nce2] */
 int wseg_loss_finish(const float* acc, float er_coef, float* out8, void* stream);
-int wseg_rvmin_backward(const float* q, const unsigned char* argc, const float* res, const float* label20, float* dU, int N, int npix, int k, float coef, void* stream);
-int wseg_norm_resize_forward(const float* U, const float* stats, const float* label20, float* out, int N, int S, int OS, void* stream);
-int wseg_norm_resize_backward(const float* G, const float* U, const float* stats, const float* label20, float* dU, int N, int S, int OS, void* stream);
 int wseg_er_ecr_prep(const float* c1, const float* c2, const float* r1, const float* r2, float* Gc1, float* Gc2, float* dlt1, float* dlt2,
                      float* er_sum, int N, int npix, float er_coef, void* stream);
 int wseg_ecr_backward(const float* dlt, const float* res, float* Gr, int N, int per_row, int k, float coef, void* stream);

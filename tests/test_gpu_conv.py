@@ -17,6 +17,30 @@ def _nhwc(x):      # [N,C,H,W] -> contiguous [N,H,W,C]
     return x.permute(0, 2, 3, 1).contiguous()
 
 
+# The kernel a hint names (wseg_hip.h: WSEG_CONV_* / WSEG_WGRAD_*).  A launch that forces a kernel goes through _conv / _wgrad, which assert through
+# the plan query (the planner the launch itself asks) that it runs there: a test named after one kernel cannot pass on another.
+CONV_FAMILY = {64: 1, 128: 2, 224: 3, 256: 4, 259: 5}
+ROWS_64_128 = (1, 2)            # where a forced 224 / 256 / 259 runs when its kernel does not take the shape: 64- or 128-row tiles
+TILE_256 = (3, 4)               # the 256-tile kernel at either tile height (no hint: the planner picks the height)
+WGRAD_128, WGRAD_PIPE = 6, 7
+
+
+def _conv(family, *tensors, perm=None, **kw):
+    """L.conv_igemm(*tensors, **kw), after asserting that its plan is `family` (one id, or a tuple of admissible ones) and, when given, `perm`."""
+    from wseg_amd import _lib as L
+    plan = L.conv_plan(*tensors, **kw)
+    assert plan.family in (family if isinstance(family, tuple) else (family,)), (plan, family)
+    assert perm is None or plan.perm == perm, (plan, perm)
+    L.conv_igemm(*tensors, **kw)
+
+
+def _wgrad(family, *tensors, **kw):
+    from wseg_amd import _lib as L
+    plan = L.wgrad_plan(*tensors, **kw)
+    assert plan.family == family, (plan, family)
+    L.conv_wgrad(*tensors, **kw)
+
+
 CASES = [
     # N, H, W, IC, OC, k, stride, dil
     (2, 20, 20, 64, 128, 3, 1, 1),
@@ -68,19 +92,20 @@ def test_conv_fwd_dgrad_wgrad(case, dt, bm):
             L.pack_x3(wt32, wt)
     # forward
     yg = torch.empty(N, OH, OW, OC, device=dev, dtype=tdt)
-    L.conv_igemm(xg, wf, yg, N=N, IH=H, IW=W, IC=IC, OH=OH, OW=OW, OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad, bm_hint=bm, dtype=cdt)
+    _conv(CONV_FAMILY[bm], xg, wf, yg, N=N, IH=H, IW=W, IC=IC, OH=OH, OW=OW, OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad, bm_hint=bm, dtype=cdt)
     np.testing.assert_allclose(yg.float().cpu().numpy(), _nhwc(y.detach()).numpy(), **tol)
     # data gradient (needs OC % (128B/es) == 0 as the reduction dim)
     es = 2 if dt == "bf16" else 4
     dyg = _nhwc(dy).to(dev, tdt)
     if (OC * es) % 128 == 0:
         dxg = torch.empty(N, H, W, IC, device=dev, dtype=tdt)
-        L.conv_igemm(dyg, wt, dxg, N=N, IH=OH, IW=OW, IC=OC, OH=H, OW=W, OC=IC, KH=k, KW=k, stride=s, dil=d, pad=pad, mode=1, bm_hint=bm, dtype=cdt)
+        _conv(CONV_FAMILY[bm], dyg, wt, dxg, N=N, IH=OH, IW=OW, IC=OC, OH=H, OW=W, OC=IC, KH=k, KW=k, stride=s, dil=d, pad=pad, mode=1, bm_hint=bm, dtype=cdt)
         np.testing.assert_allclose(dxg.float().cpu().numpy(), _nhwc(x.grad).numpy(), **tol)
-    # weight gradient (f32, accumulating)
+    # weight gradient (f32, accumulating); tile_hint 256 takes the 256 x 256 pipe kernel where it exists (bf16, IC and OC >= 256), else the 128-tile one
     dwg = torch.zeros(OC, k * k, IC, device=dev, dtype=torch.float32)
-    L.conv_wgrad(xg, dyg, dwg, N=N, IH=H, IW=W, IC=IC, OH=OH, OW=OW, OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad,
-                 tile_hint=256 if bm == 128 else 128, dtype=cdt)
+    pipe = bm == 128 and dt == "bf16" and IC >= 256 and OC >= 256
+    _wgrad(WGRAD_PIPE if pipe else WGRAD_128, xg, dyg, dwg, N=N, IH=H, IW=W, IC=IC, OH=OH, OW=OW, OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad,
+           tile_hint=256 if bm == 128 else 128, dtype=cdt)
     ref = w.grad.permute(0, 2, 3, 1).reshape(OC, k * k, IC).numpy()
     scale = np.abs(ref).max()
     wtol = {"f32": 2e-5, "x3": 1e-4, "bf16": 1e-2}[dt]
@@ -111,9 +136,10 @@ def test_conv_epilogues(dt, OC, bm):
     wf = w.permute(0, 2, 3, 1).reshape(OC, k * k, IC).contiguous().to(dev, tdt)
     out = torch.empty(N, H, W, OC, device=dev, dtype=tdt)
     out2 = torch.empty(N, H, W, OC, device=dev, dtype=tdt)
-    L.conv_igemm(xg, wf, out, out2, N=N, IH=H, IW=W, IC=IC, OH=H, OW=W, OC=OC, KH=k, KW=k, pad=1,
-                 r_pre=_nhwc(pre).to(dev, tdt), r_post=_nhwc(res).to(dev, tdt),
-                 scale=scale.to(dev), shift=shift.to(dev), drop=drop.to(dev), bm_hint=bm)
+    fam = CONV_FAMILY[bm] if bm else ROWS_64_128           # (no hint, OC = 128, 300 rows: the planner stays on the 64 / 128-row tiles)
+    _conv(fam, xg, wf, out, out2, N=N, IH=H, IW=W, IC=IC, OH=H, OW=W, OC=OC, KH=k, KW=k, pad=1,
+          r_pre=_nhwc(pre).to(dev, tdt), r_post=_nhwc(res).to(dev, tdt),
+          scale=scale.to(dev), shift=shift.to(dev), drop=drop.to(dev), bm_hint=bm)
     tol = dict(rtol=2e-5, atol=2e-5) if dt == "f32" else dict(rtol=2e-2, atol=3e-2)
     np.testing.assert_allclose(out.float().cpu().numpy(), _nhwc(raw).numpy(), **tol)
     # out2 is computed from the unrounded sum in-kernel; compare loosely in bf16
@@ -121,14 +147,14 @@ def test_conv_epilogues(dt, OC, bm):
     # epi 1: (acc + pre) * scale * drop * (mask > 0) + post
     mask = _rand((N, OC, H, W), 9)
     exp = (y + pre) * scale.view(1, -1, 1, 1) * drop.view(N, OC, 1, 1) * (mask > 0).float() + res
-    L.conv_igemm(xg, wf, out, N=N, IH=H, IW=W, IC=IC, OH=H, OW=W, OC=OC, KH=k, KW=k, pad=1, epi=1,
-                 r_pre=_nhwc(pre).to(dev, tdt), r_post=_nhwc(res).to(dev, tdt), mask=_nhwc(mask).to(dev, tdt),
-                 scale=scale.to(dev), drop=drop.to(dev), bm_hint=bm)
+    _conv(fam, xg, wf, out, N=N, IH=H, IW=W, IC=IC, OH=H, OW=W, OC=OC, KH=k, KW=k, pad=1, epi=1,
+          r_pre=_nhwc(pre).to(dev, tdt), r_post=_nhwc(res).to(dev, tdt), mask=_nhwc(mask).to(dev, tdt),
+          scale=scale.to(dev), drop=drop.to(dev), bm_hint=bm)
     np.testing.assert_allclose(out.float().cpu().numpy(), _nhwc(exp).numpy(), **tol)
     # epi 2 with an output row stride and channel offset (writes into a wider buffer)
     wide = torch.zeros(N, H, W, OC + 128, device=dev, dtype=tdt)
-    L.conv_igemm(xg, wf, wide[..., 64:], N=N, IH=H, IW=W, IC=IC, OH=H, OW=W, OC=OC, KH=k, KW=k, pad=1, epi=2, ld_out=OC + 128,
-                 bm_hint=bm)
+    _conv(fam, xg, wf, wide[..., 64:], N=N, IH=H, IW=W, IC=IC, OH=H, OW=W, OC=OC, KH=k, KW=k, pad=1, epi=2, ld_out=OC + 128,
+          bm_hint=bm)
     np.testing.assert_allclose(wide[..., 64:64 + OC].float().cpu().numpy(), _nhwc(F.relu(y)).numpy(), **tol)
     assert float(wide[..., :64].abs().max()) == 0 and float(wide[..., 64 + OC:].abs().max()) == 0
 
@@ -203,18 +229,27 @@ def test_conv_two_row_segments(dt, bm, geom):
     O1, O2 = (osz(H1), osz(W1)), (osz(H2), osz(W2))
     seg_f = (H2, W2, O2[0], O2[1])
     yg = torch.empty(dyj.shape[0], OC, device=dev, dtype=tdt)
-    L.conv_igemm(xj, wf, yg, N=N, IH=H1, IW=W1, IC=IC, OH=O1[0], OW=O1[1], OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad, seg2=seg_f, bm_hint=bm)
+    fam = CONV_FAMILY.get(bm)                               # (bm 0: no kernel is named)
+
+    def conv(family, *tensors, perm=None, **kw):
+        _conv(family, *tensors, perm=perm, **kw) if bm else L.conv_igemm(*tensors, **kw)
+    conv(fam, xj, wf, yg, N=N, IH=H1, IW=W1, IC=IC, OH=O1[0], OW=O1[1], OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad, seg2=seg_f, bm_hint=bm)
     tol = dict(rtol=2e-5, atol=2e-5) if dt == "f32" else dict(rtol=2e-2, atol=2e-2)
     np.testing.assert_allclose(yg.float().cpu().numpy(), torch.cat([rows(y.detach()) for y in ys]).numpy(), **tol)
     dxg = torch.empty(xj.shape[0], IC, device=dev, dtype=tdt)
-    L.conv_igemm(dyj, wt, dxg, N=N, IH=O1[0], IW=O1[1], IC=OC, OH=H1, OW=W1, OC=IC, KH=k, KW=k, stride=s, dil=d, pad=pad, mode=1,
-                 seg2=(O2[0], O2[1], H2, W2), bm_hint=bm)
+    # the 512 x 128 kernel has no strided data gradient: a forced 259 then runs on the 64 / 128-row tiles (same numeric check).  Parity-ordered rows
+    # (perm): stride-2 data gradient on the 256-tile kernel with even sizes in both segments, 3x3 — or 1x1 when 256 is forced
+    dfam = ROWS_64_128 if (bm == 259 and s != 1) else fam
+    perm = None if bm not in (224, 256) else int(s == 2 and H2 % 2 == 0 and (k == 3 or bm == 256))
+    conv(dfam, dyj, wt, dxg, N=N, IH=O1[0], IW=O1[1], IC=OC, OH=H1, OW=W1, OC=IC, KH=k, KW=k, stride=s, dil=d, pad=pad, mode=1,
+         seg2=(O2[0], O2[1], H2, W2), bm_hint=bm, perm=perm)
     np.testing.assert_allclose(dxg.float().cpu().numpy(), torch.cat([rows(x.grad) for x in xs]).numpy(), **tol)
     ref = w.grad.permute(0, 2, 3, 1).reshape(OC, k * k, IC).numpy()
     for hint in (128, 256):
         dwg = torch.zeros(OC, k * k, IC, device=dev, dtype=torch.float32)
-        L.conv_wgrad(xj, dyj, dwg, N=N, IH=H1, IW=W1, IC=IC, OH=O1[0], OW=O1[1], OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad,
-                     seg2=seg_f, tile_hint=hint, split_k=2)
+        pipe = hint == 256 and dt == "bf16" and IC >= 256     # (OC = 256; f32 and IC = 64 have no 256 x 256 kernel: the 128-tile one runs)
+        _wgrad(WGRAD_PIPE if pipe else WGRAD_128, xj, dyj, dwg, N=N, IH=H1, IW=W1, IC=IC, OH=O1[0], OW=O1[1], OC=OC, KH=k, KW=k, stride=s, dil=d,
+               pad=pad, seg2=seg_f, tile_hint=hint, split_k=2)
         assert np.abs(dwg.cpu().numpy() - ref).max() / np.abs(ref).max() < (2e-5 if dt == "f32" else 1e-2)
 
 
@@ -252,33 +287,34 @@ def test_conv256_fwd_dgrad(case):
     L.pack_weights(wm, wf, wt, OC, k * k, IC, OC, IC, L.dtype_code(wf))
     tol = dict(rtol=2e-2, atol=2e-2)
     yg = torch.empty(N, OH, OW, OC, device=dev, dtype=tdt)
-    L.conv_igemm(xg, wf, yg, N=N, IH=H, IW=W, IC=IC, OH=OH, OW=OW, OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad, bm_hint=256)
+    _conv(CONV_FAMILY[256], xg, wf, yg, N=N, IH=H, IW=W, IC=IC, OH=OH, OW=OW, OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad, bm_hint=256)
     np.testing.assert_allclose(yg.float().cpu().numpy(), _nhwc(y.detach()).numpy(), **tol)
     # the two tile geometries must agree to accumulation-order noise
     y128 = torch.empty_like(yg)
-    L.conv_igemm(xg, wf, y128, N=N, IH=H, IW=W, IC=IC, OH=OH, OW=OW, OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad, bm_hint=128)
+    _conv(CONV_FAMILY[128], xg, wf, y128, N=N, IH=H, IW=W, IC=IC, OH=OH, OW=OW, OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad, bm_hint=128)
     assert float((yg.float() - y128.float()).abs().max()) <= 2e-2
     # 224-row tiles of the 256-tile kernel (each wave row owns 112 rows)
     y7 = torch.full_like(yg, float("nan"))
-    L.conv_igemm(xg, wf, y7, N=N, IH=H, IW=W, IC=IC, OH=OH, OW=OW, OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad, bm_hint=224)
+    _conv(CONV_FAMILY[224], xg, wf, y7, N=N, IH=H, IW=W, IC=IC, OH=OH, OW=OW, OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad, bm_hint=224)
     np.testing.assert_allclose(y7.float().cpu().numpy(), _nhwc(y.detach()).numpy(), **tol)
     # the 512 x 128 tile kernel (four stacked A half-tiles, all 160 KiB of LDS)
     y5 = torch.full_like(yg, float("nan"))
-    L.conv_igemm(xg, wf, y5, N=N, IH=H, IW=W, IC=IC, OH=OH, OW=OW, OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad, bm_hint=259)
+    _conv(CONV_FAMILY[259], xg, wf, y5, N=N, IH=H, IW=W, IC=IC, OH=OH, OW=OW, OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad, bm_hint=259)
     np.testing.assert_allclose(y5.float().cpu().numpy(), _nhwc(y.detach()).numpy(), **tol)
     if s == 1 and IC % 128 == 0:
         dx5 = torch.full((N, H, W, IC), float("nan"), device=dev, dtype=tdt)
-        L.conv_igemm(_nhwc(dy).to(dev, tdt), wt, dx5, N=N, IH=OH, IW=OW, IC=OC, OH=H, OW=W, OC=IC, KH=k, KW=k, stride=s, dil=d,
-                     pad=pad, mode=1, bm_hint=259)
+        _conv(CONV_FAMILY[259], _nhwc(dy).to(dev, tdt), wt, dx5, N=N, IH=OH, IW=OW, IC=OC, OH=H, OW=W, OC=IC, KH=k, KW=k, stride=s, dil=d,
+              pad=pad, mode=1, bm_hint=259)
         np.testing.assert_allclose(dx5.float().cpu().numpy(), _nhwc(x.grad).numpy(), **tol)
     if IC % 256 == 0:                     # dgrad: the conv's IC is the GEMM's N
         dxg = torch.empty(N, H, W, IC, device=dev, dtype=tdt)
-        L.conv_igemm(_nhwc(dy).to(dev, tdt), wt, dxg, N=N, IH=OH, IW=OW, IC=OC, OH=H, OW=W, OC=IC, KH=k, KW=k, stride=s, dil=d,
-                     pad=pad, mode=1, bm_hint=256)
+        even = s == 2 and H % 2 == 0 and W % 2 == 0        # the stride-2 data gradient walks its rows in parity-class order (1x1: only when 256 is forced)
+        _conv(CONV_FAMILY[256], _nhwc(dy).to(dev, tdt), wt, dxg, N=N, IH=OH, IW=OW, IC=OC, OH=H, OW=W, OC=IC, KH=k, KW=k, stride=s, dil=d,
+              pad=pad, mode=1, bm_hint=256, perm=int(even))
         np.testing.assert_allclose(dxg.float().cpu().numpy(), _nhwc(x.grad).numpy(), **tol)
         dx7 = torch.full_like(dxg, float("nan"))
-        L.conv_igemm(_nhwc(dy).to(dev, tdt), wt, dx7, N=N, IH=OH, IW=OW, IC=OC, OH=H, OW=W, OC=IC, KH=k, KW=k, stride=s, dil=d,
-                     pad=pad, mode=1, bm_hint=224)
+        _conv(CONV_FAMILY[224], _nhwc(dy).to(dev, tdt), wt, dx7, N=N, IH=OH, IW=OW, IC=OC, OH=H, OW=W, OC=IC, KH=k, KW=k, stride=s, dil=d,
+              pad=pad, mode=1, bm_hint=224, perm=int(even and k == 3))
         np.testing.assert_allclose(dx7.float().cpu().numpy(), _nhwc(x.grad).numpy(), **tol)
 
 
@@ -313,13 +349,10 @@ def test_conv_bwd_pair(geom):
     L.conv_wgrad(xj, dyj, dw_a, **wkw)
     dx_b = torch.full_like(dx_a, float("nan"))
     dw_b = torch.zeros_like(dw_a)
-    L.TRACK_PAIRS = True
-    try:
-        L.conv_igemm(dyj, wt, dx_b, IH=H, IW=W, IC=OC, OH=H, OW=W, OC=IC, mode=1, pair_wgrad=(xj, dyj, dw_b, wkw), **geo)
-        fused = L.LAST_PAIR_FUSED
-    finally:
-        L.TRACK_PAIRS = False
+    fused, dg_plan, wg_plan = L.conv_pair_plan(wkw, dyj, wt, dx_b, IH=H, IW=W, IC=OC, OH=H, OW=W, OC=IC, mode=1, **geo)
     assert fused == (0 if H == 40 else 1)
+    assert not fused or (dg_plan.family in TILE_256 and dg_plan.tapf == 1 and wg_plan.family == WGRAD_PIPE)
+    L.conv_igemm(dyj, wt, dx_b, IH=H, IW=W, IC=OC, OH=H, OW=W, OC=IC, mode=1, pair_wgrad=(xj, dyj, dw_b, wkw), **geo)
     assert torch.equal(dx_a, dx_b)
     ref_dx = torch.cat([rows(x.grad) for x in xs]).numpy()
     np.testing.assert_allclose(dx_b.float().cpu().numpy(), ref_dx, rtol=2e-2, atol=2e-2)
@@ -349,12 +382,9 @@ def test_conv_bwd_pair_two_sources():
     dw_a = torch.zeros(C1, 1, OCd, device=dev, dtype=torch.float32)
     L.conv_wgrad(t, D, dw_a, **wkw)
     dx_b, dw_b = torch.full_like(dx_a, float("nan")), torch.zeros_like(dw_a)
-    L.TRACK_PAIRS = True
-    try:
-        L.conv_igemm(D, wcat, dx_b, pair_wgrad=(t, D, dw_b, wkw), **kw)
-        assert L.LAST_PAIR_FUSED == 1
-    finally:
-        L.TRACK_PAIRS = False
+    fused, dg_plan, wg_plan = L.conv_pair_plan(wkw, D, wcat, dx_b, **kw)
+    assert fused == 1 and dg_plan.family in TILE_256 and wg_plan.family == WGRAD_PIPE
+    L.conv_igemm(D, wcat, dx_b, pair_wgrad=(t, D, dw_b, wkw), **kw)
     assert torch.equal(dx_a, dx_b) and torch.isfinite(dx_b.float()).all()
     ref = (D.float() @ wcat[:, 0, :C1].float().t() + du1.float() @ wcat[:, 0, C1:].float().t()) * scale * (mask.float() != 0)
     np.testing.assert_allclose(dx_b.float().cpu().numpy(), ref.cpu().numpy(), rtol=2e-2, atol=3e-2)
@@ -397,8 +427,8 @@ def test_conv256_split_bf16(case):
     for bm in (256, 224, 128):
         yg = torch.full((N, OH, OW, OC), float("nan"), device=dev)
         tg = torch.full((N, OH, OW, OC), float("nan"), device=dev)
-        L.conv_igemm(xg, wf, yg, tg, N=N, IH=H, IW=W, IC=IC, OH=OH, OW=OW, OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad, bm_hint=bm,
-                     r_post=_nhwc(res).to(dev), scale=scale.to(dev), shift=shift.to(dev), dtype=L.F32X3)
+        _conv(CONV_FAMILY[bm], xg, wf, yg, tg, N=N, IH=H, IW=W, IC=IC, OH=OH, OW=OW, OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad, bm_hint=bm,
+              r_post=_nhwc(res).to(dev), scale=scale.to(dev), shift=shift.to(dev), dtype=L.F32X3)
         np.testing.assert_allclose(yg.cpu().numpy(), y_ref, **tol)
         np.testing.assert_allclose(tg.cpu().numpy(), t_ref, **tol)
     if IC % 256 == 0:                     # dgrad: the conv's IC is the GEMM's N; BN-ReLU backward epilogue (mask = saved activation)
@@ -407,8 +437,8 @@ def test_conv256_split_bf16(case):
         dx_ref = _nhwc(x.grad * sc_in.view(1, -1, 1, 1) * (mask > 0)).numpy()
         for bm in (256, 224, 128):
             dxg = torch.full((N, H, W, IC), float("nan"), device=dev)
-            L.conv_igemm(_nhwc(dy).to(dev), wt, dxg, N=N, IH=OH, IW=OW, IC=OC, OH=H, OW=W, OC=IC, KH=k, KW=k, stride=s, dil=d,
-                         pad=pad, mode=1, bm_hint=bm, epi=1, scale=sc_in.to(dev), mask=_nhwc(mask).to(dev), dtype=L.F32X3)
+            _conv(CONV_FAMILY[bm], _nhwc(dy).to(dev), wt, dxg, N=N, IH=OH, IW=OW, IC=OC, OH=H, OW=W, OC=IC, KH=k, KW=k, stride=s, dil=d,
+                  pad=pad, mode=1, bm_hint=bm, epi=1, scale=sc_in.to(dev), mask=_nhwc(mask).to(dev), dtype=L.F32X3)
             np.testing.assert_allclose(dxg.cpu().numpy(), dx_ref, **tol)
 
 
@@ -461,8 +491,8 @@ def test_conv_two_sources(bm, IC2):
     wcat = torch.cat([w1.reshape(OC, 1, IC), w2.reshape(OC, 1, IC2)], dim=2).contiguous().to(dev, tdt)   # rows [W1[oc] | W2[oc]]
     out = torch.full((a.shape[0], OC), float("nan"), device=dev, dtype=tdt)
     out2 = torch.full_like(out, float("nan"))
-    L.conv_igemm(a, wcat, out, out2, N=N, IH=H1, IW=W1, IC=IC, OH=H1, OW=W1, OC=OC, KH=1, KW=1, seg2=(H2, W2, H2, W2),
-                 in2=b, IC2=IC2, ld_in2=IC2 + 64, scale=scale.to(dev), shift=shift.to(dev), drop=drop.to(dev), bm_hint=bm)
+    _conv(CONV_FAMILY[224] if bm else TILE_256, a, wcat, out, out2, N=N, IH=H1, IW=W1, IC=IC, OH=H1, OW=W1, OC=OC, KH=1, KW=1, seg2=(H2, W2, H2, W2),
+          in2=b, IC2=IC2, ld_in2=IC2 + 64, scale=scale.to(dev), shift=shift.to(dev), drop=drop.to(dev), bm_hint=bm)
     tol = dict(rtol=2e-2, atol=2e-2)
     np.testing.assert_allclose(out.float().cpu().numpy(), ref.numpy(), **tol)
     np.testing.assert_allclose(out2.float().cpu().numpy(), act.numpy(), rtol=2e-2, atol=4e-2)
@@ -491,7 +521,7 @@ def test_conv_two_sources_3x3(dil, IC2):
     b = torch.cat([rows(t) for t in x2]).to(dev, tdt)
     wcat = torch.cat([w1.permute(0, 2, 3, 1).reshape(OC, 9 * IC), w2.reshape(OC, IC2)], dim=1).contiguous().to(dev, tdt)
     out = torch.full((a.shape[0], OC), float("nan"), device=dev, dtype=tdt)
-    L.conv_igemm(a, wcat, out, N=N, IH=H1, IW=W1, IC=IC, OH=H1, OW=W1, OC=OC, KH=k, KW=k, dil=dil, pad=pad, seg2=(H2, W2, H2, W2), in2=b, IC2=IC2)
+    _conv(TILE_256, a, wcat, out, N=N, IH=H1, IW=W1, IC=IC, OH=H1, OW=W1, OC=OC, KH=k, KW=k, dil=dil, pad=pad, seg2=(H2, W2, H2, W2), in2=b, IC2=IC2)
     tol = dict(rtol=2e-2, atol=2e-2)
     np.testing.assert_allclose(out.float().cpu().numpy(), ref.numpy(), **tol)
     # mode 1: dX = dgrad_3x3(dY1; V1) + dY2 . V2 for convolutions V1 [OCv][IC_v][3][3] (input = this test's output side) and V2 1x1
@@ -501,5 +531,5 @@ def test_conv_two_sources_3x3(dil, IC2):
     refd = torch.cat([rows(F.conv_transpose2d(dy1, v1, None, 1, pad, 0, 1, dil) + F.conv_transpose2d(dy2, v2)) for dy1, dy2 in zip(x1, x2)])
     wt = torch.cat([v1.permute(1, 2, 3, 0).reshape(OC, 9 * OCv), v2.reshape(IC2, OC).t()], dim=1).contiguous().to(dev, tdt)   # [OC][9*OCv + IC2]
     dx = torch.full((a.shape[0], OC), float("nan"), device=dev, dtype=tdt)
-    L.conv_igemm(a, wt, dx, N=N, IH=H1, IW=W1, IC=OCv, OH=H1, OW=W1, OC=OC, KH=k, KW=k, dil=dil, pad=pad, mode=1, seg2=(H2, W2, H2, W2), in2=b, IC2=IC2)
+    _conv(TILE_256, a, wt, dx, N=N, IH=H1, IW=W1, IC=OCv, OH=H1, OW=W1, OC=OC, KH=k, KW=k, dil=dil, pad=pad, mode=1, seg2=(H2, W2, H2, W2), in2=b, IC2=IC2)
     np.testing.assert_allclose(dx.float().cpu().numpy(), refd.numpy(), **tol)

@@ -78,7 +78,7 @@ lib = _load()
 
 
 def _ptr(t):
-    return None if t is None else t.data_ptr()
+    return t.data_ptr() if torch.is_tensor(t) else t       # (None; or an int: the plan queries take stand-in addresses)
 
 
 def stream_ptr():
@@ -115,9 +115,6 @@ def dtype_code(t):
     raise TypeError(f"unsupported dtype {t.dtype}")
 
 
-TRACK_PAIRS, LAST_PAIR_FUSED = False, None        # tests: whether the last pair_wgrad launch was ONE grid
-
-
 def _flops_label(kind, *, N, IH, IW, IC, OH, OW, OC, KH, KW, stride=1, dil=1, seg2=None, mode=0, IC2=None, **_):
     """(algorithmic FLOPs, label) of a conv / wgrad launch for the profiler.  Pixels counted: the CONV's output pixels — the launch's
     input side for a data gradient (mode 1); IC2: channels of a second source."""
@@ -142,12 +139,35 @@ def _timed(sink, entry):
     sink.append((ev0, ev1) + tuple(entry()))
 
 
-def conv_igemm(inp, w, out=None, out2=None, *, N, IH, IW, IC, OH, OW, OC, KH, KW, stride=1, dil=1, pad=0,
+def conv_igemm(inp, w, out=None, out2=None, *, pair_wgrad=None, **kw):
+    """One conv launch; `kw`: the keywords of _conv_desc.  w_rows: rows of the weight pack when it is zero-padded beyond OC (wseg_conv_desc.w_rows).
+    pair_wgrad: (x, dy, dw, kwargs of conv_wgrad) — a weight gradient launched in the SAME grid as this data gradient (wseg_conv_bwd_pair; the
+    library falls back to two launches when the pair does not qualify: conv_pair_plan tells)."""
+    d = _conv_desc(inp, w, out, out2, **kw)
+    ic2 = (d.IC2 or d.IC) if d.in2 else 0        # two sources: w = [OC][KH*KW*IC + IC2]
+    krow, wrows = d.KH * d.KW * d.IC + ic2, max(d.OC, d.w_rows)
+    if w.numel() < wrows * krow:                 # (raw pointers beyond this line: a short weight buffer would be read out of bounds)
+        raise RuntimeError(f"conv_igemm: weight buffer has {w.numel()} elements, the launch reads {wrows} x {krow}")
+    sampled, launch_idx = _profile_sample() if PROFILE is not None else (False, 0)
+
+    def entry():
+        kind = "fwd" if d.mode == 0 else ("dgrad+wgrad" if pair_wgrad is not None else "dgrad")
+        flops, label = _flops_label(kind, **{**kw, "IC2": ic2})
+        wflops = _flops_label("wgrad", **pair_wgrad[3])[0] if pair_wgrad is not None else 0.0
+        return flops + wflops, label, launch_idx
+
+    with _timed(PROFILE if sampled else None, entry):        # bench.py: HIP events on the launch stream around this launch
+        if pair_wgrad is not None:
+            wx, wdy, wdw, wkw = pair_wgrad
+            _call("wseg_conv_bwd_pair", C.byref(d), C.byref(_wgrad_desc(wx, wdy, wdw, **wkw)))
+        else:
+            _call("wseg_conv_igemm", C.byref(d))
+
+
+def _conv_desc(inp, w, out, out2, *, N, IH, IW, IC, OH, OW, OC, KH, KW, stride=1, dil=1, pad=0,
                mode=0, epi=0, r_pre=None, r_post=None, mask=None, scale=None, shift=None, drop=None,
                ld_in=None, ld_out=None, ld_out2=None, ld_rpre=None, ld_rpost=None, ld_mask=None, relu_out2=1,
-               relu_lt=0, bm_hint=0, seg2=None, in2=None, ld_in2=None, IC2=0, dtype=None, pair_wgrad=None, w_rows=0):
-    """w_rows: rows of the weight pack when it is zero-padded beyond OC (wseg_conv_desc.w_rows).  pair_wgrad: (x, dy, dw, kwargs of conv_wgrad) — a weight gradient launched in the SAME grid as this data gradient (wseg_conv_bwd_pair; the
-    library falls back to two launches when the pair does not qualify)."""
+               relu_lt=0, bm_hint=0, seg2=None, in2=None, ld_in2=None, IC2=0, dtype=None, w_rows=0):
     d = ConvDesc()
     d.inp, d.w, d.out, d.out2 = _ptr(inp), _ptr(w), _ptr(out), _ptr(out2)
     d.r_pre, d.r_post, d.mask = _ptr(r_pre), _ptr(r_post), _ptr(mask)
@@ -162,28 +182,8 @@ def conv_igemm(inp, w, out=None, out2=None, *, N, IH, IW, IC, OH, OW, OC, KH, KW
     ic2 = (IC2 or IC) if in2 is not None else 0  # two sources: w = [OC][KH*KW*IC + IC2]
     if in2 is not None:
         d.in2, d.IC2, d.ld_in2 = _ptr(in2), IC2, ld_in2 or ic2
-    krow = KH * KW * IC + ic2
     d.w_rows = w_rows
-    if w.numel() < max(OC, w_rows) * krow:       # (raw pointers beyond this line: a short weight buffer would be read out of bounds)
-        raise RuntimeError(f"conv_igemm: weight buffer has {w.numel()} elements, the launch reads {max(OC, w_rows)} x {krow}")
-    sampled, launch_idx = _profile_sample() if PROFILE is not None else (False, 0)
-
-    def entry():
-        kind = "fwd" if mode == 0 else ("dgrad+wgrad" if pair_wgrad is not None else "dgrad")
-        flops, label = _flops_label(kind, N=N, IH=IH, IW=IW, IC=IC, OH=OH, OW=OW, OC=OC, KH=KH, KW=KW, stride=stride, dil=dil, seg2=seg2,
-                                    mode=mode, IC2=ic2)
-        wflops = _flops_label("wgrad", **pair_wgrad[3])[0] if pair_wgrad is not None else 0.0
-        return flops + wflops, label, launch_idx
-
-    with _timed(PROFILE if sampled else None, entry):        # bench.py: HIP events on the launch stream around this launch
-        if pair_wgrad is not None:
-            wx, wdy, wdw, wkw = pair_wgrad
-            wd = _wgrad_desc(wx, wdy, wdw, **wkw)
-            global LAST_PAIR_FUSED
-            LAST_PAIR_FUSED = lib.wseg_conv_bwd_pair_fuses(C.byref(d), C.byref(wd)) if TRACK_PAIRS else None
-            _call("wseg_conv_bwd_pair", C.byref(d), C.byref(wd))
-        else:
-            _call("wseg_conv_igemm", C.byref(d))
+    return d
 
 
 def _wgrad_desc(x, dy, dw, *, N, IH, IW, IC, OH, OW, OC, KH, KW, stride=1, dil=1, pad=0,
@@ -198,7 +198,7 @@ def _wgrad_desc(x, dy, dw, *, N, IH, IW, IC, OH, OW, OC, KH, KW, stride=1, dil=1
     d.dw_rot = dw_rot
     if seg2 is not None:
         d.IH2, d.IW2, d.OH2, d.OW2 = seg2
-    assert dw.dtype == torch.float32
+    assert not torch.is_tensor(dw) or dw.dtype == torch.float32
     return d
 
 
@@ -207,6 +207,50 @@ def conv_wgrad(x, dy, dw, **kw):
     d = _wgrad_desc(x, dy, dw, **kw)
     with _timed(PROFILE_WGRAD, lambda: _flops_label("wgrad", **kw)):
         _call("wseg_conv_wgrad", C.byref(d))
+
+
+# ---- what a launch would run (wseg_conv_plan / wseg_wgrad_plan / wseg_conv_bwd_pair_plan): pure host arithmetic, works without a GPU
+CONV_64x128, CONV_128x128, CONV_224x256, CONV_256x256, CONV_512x128, WGRAD_128x128, WGRAD_256x256 = range(1, 8)     # WSEG_CONV_* / WSEG_WGRAD_*
+_ANY = 64             # stand-in address of a tensor the caller does not have: the planners only test pointers against NULL
+
+
+class LaunchPlan(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("family", "tile_rows", "tile_cols", "nwg", "perm", "tapf", "nsplit", "unit")]
+
+    def __repr__(self):
+        return "LaunchPlan(" + ", ".join(f"{k}={getattr(self, k)}" for k, _t in self._fields_) + ")"
+
+
+def _plan_dtype(t, dtype):
+    return dtype if dtype is not None else (dtype_code(t) if torch.is_tensor(t) else BF16)
+
+
+def conv_plan(inp=_ANY, w=_ANY, out=_ANY, out2=None, *, dtype=None, **kw):
+    """The plan of conv_igemm(inp, w, out, out2, **kw) — the same keywords; the tensors may be left out (bf16 unless `dtype` says otherwise)."""
+    plan = LaunchPlan()
+    check(lib.wseg_conv_plan(C.byref(_conv_desc(inp, w, out, out2, dtype=_plan_dtype(inp, dtype), **kw)), C.byref(plan)), "wseg_conv_plan")
+    return plan
+
+
+def wgrad_plan(x=_ANY, dy=_ANY, dw=_ANY, *, dtype=None, **kw):
+    """The plan of conv_wgrad(x, dy, dw, **kw)."""
+    plan = LaunchPlan()
+    check(lib.wseg_wgrad_plan(C.byref(_wgrad_desc(x, dy, dw, dtype=_plan_dtype(x, dtype), **kw)), C.byref(plan)), "wseg_wgrad_plan")
+    return plan
+
+
+def conv_pair_plan(wgrad_kw, inp=_ANY, w=_ANY, out=_ANY, out2=None, *, dtype=None, **kw):
+    """The plan of conv_igemm(inp, w, out, out2, pair_wgrad=(x, dy, dw, wgrad_kw), **kw): (fused, data-gradient plan, weight-gradient plan);
+    fused 1 = one grid, 0 = the two ordinary launches.  The weight gradient is planned in the data gradient's dtype unless wgrad_kw carries a
+    `dtype` of its own (conv_igemm takes it from the tensor x; the engine's pairs are of one dtype)."""
+    dg, wg = LaunchPlan(), LaunchPlan()
+    dtype = _plan_dtype(inp, dtype)
+    wdtype = dtype if wgrad_kw.get("dtype") is None else wgrad_kw["dtype"]
+    fused = lib.wseg_conv_bwd_pair_plan(C.byref(_conv_desc(inp, w, out, out2, dtype=dtype, **kw)),
+                                        C.byref(_wgrad_desc(_ANY, _ANY, _ANY, **{**wgrad_kw, "dtype": wdtype})), C.byref(dg), C.byref(wg))
+    if fused < 0:                                # (0 and 1 are both answers here)
+        check(fused, "wseg_conv_bwd_pair_plan")
+    return fused, dg, wg
 
 
 def pack_weights(master, fwd, tr, OC, T, IC, OCp, ICp, dtype, ic_rot=0):
@@ -298,14 +342,10 @@ def plane_stats(U, stats, planes, npix):
     ws = torch.empty(int(lib.wseg_plane_stats_workspace_bytes(C.c_long(planes))), device=U.device, dtype=torch.uint8)
     _call("wseg_plane_stats", _v(U), _v(stats), C.c_long(planes), npix, _v(ws))
 def cls_loss(stats, label20, loss_out, plane_bias, N, npix, coef): _call("wseg_cls_loss", _v(stats), _v(label20), _v(loss_out), _v(plane_bias), N, npix, _f(coef))
-def rvmin_values(U, label20, q, argc, N, npix): _call("wseg_rvmin_values", _v(U), _v(label20), _v(q), _v(argc), N, npix)
 def select_workspace_bytes(rows): return int(lib.wseg_select_workspace_bytes(rows))
 def select_kth(vals, rows, n, k, largest, use_abs, relu_vals, res, ws): _call("wseg_select_kth", _v(vals), rows, n, k, int(largest), int(use_abs), int(relu_vals), _v(res), _v(ws))
 def loss_finish(acc, er_coef, out8): _call("wseg_loss_finish", _v(acc), _f(er_coef), _v(out8))
 def select_finish(res, rows, k, relu_vals, scale, loss_out): _call("wseg_select_finish", _v(res), rows, k, int(relu_vals), _f(scale), _v(loss_out))
-def rvmin_backward(q, argc, res, label20, dU, N, npix, k, coef): _call("wseg_rvmin_backward", _v(q), _v(argc), _v(res), _v(label20), _v(dU), N, npix, k, _f(coef))
-def norm_resize_forward(U, stats, label20, out, N, S, OS): _call("wseg_norm_resize_forward", _v(U), _v(stats), _v(label20), _v(out), N, S, OS)
-def norm_resize_backward(G, U, stats, label20, dU, N, S, OS): _call("wseg_norm_resize_backward", _v(G), _v(U), _v(stats), _v(label20), _v(dU), N, S, OS)
 def er_ecr_prep(c1, c2, r1, r2, Gc1, Gc2, dlt1, dlt2, er_sum, N, npix, er_coef): _call("wseg_er_ecr_prep", _v(c1), _v(c2), _v(r1), _v(r2), _v(Gc1), _v(Gc2), _v(dlt1), _v(dlt2), _v(er_sum), N, npix, _f(er_coef))
 def ecr_backward(dlt, res, Gr, N, per_row, k, coef): _call("wseg_ecr_backward", _v(dlt), _v(res), _v(Gr), N, per_row, k, _f(coef))
 def rows_resize_forward(head, ld, F, N, ih, iw, oh, ow): _call("wseg_rows_resize_forward", _v(head), ld, _v(F), N, ih, iw, oh, ow, dtype_code(head))

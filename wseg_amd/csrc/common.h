@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <type_traits>
 #include "../../include/wseg_hip.h"
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
@@ -133,6 +134,16 @@ __device__ __forceinline__ wseg_rowgeo wseg_decode_row(const D& d, int m) {
     g.in_base = (long)d.N * d.IH * d.IW + (long)n * d.IH2 * d.IW2;
   }
   return g;
+}
+
+// A run-time value as a template argument: calls f(std::integral_constant<int, v>) for v in [0, N) (a v outside the range takes N - 1 or 0).
+// The launch functions nest one call per template parameter of the kernel they pick.
+template <int N, class F>
+static inline void with_const(int v, F&& f) {
+  if constexpr (N > 1) {
+    if (v < N - 1) return with_const<N - 1>(v, f);
+  }
+  f(std::integral_constant<int, N - 1>{});
 }
 
 void wseg_set_error(const char* fmt, ...);

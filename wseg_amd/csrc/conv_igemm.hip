@@ -15,14 +15,6 @@
 #include "common.h"
 #include "conv_wgrad_kernels.h"   // (wseg_wg::…: the weight-gradient tile body and its host-side plan, for wseg_conv_bwd_pair)
 
-#ifdef WSEG_PROBES   // timing diagnostics of probe builds: bm_hint -1 / -2 feed A / B from the zero page (results wrong by design)
-#define WSEG_DIAG_ZERO_A(d) ((d).bm_hint == -1)
-#define WSEG_DIAG_ZERO_B(d) ((d).bm_hint == -2)
-#else
-#define WSEG_DIAG_ZERO_A(d) false
-#define WSEG_DIAG_ZERO_B(d) false
-#endif
-
 #ifdef WSEG_PROBES
 // In-kernel stamps of the 256-tile body (probe builds only: `WSEG_PROBES=1 bash build.sh`): per workgroup 8 x s_memrealtime (100 MHz) — entry, gather
 // set-up done, first tiles landed, main loop done (early wave group), tile done; slots 5 / 6: main loop / tile done of the late group (wave 4);
@@ -468,7 +460,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const Args a) {
     const int r = wid * 32 + i * 8 + srow;         // row inside the B tile
     lch[i] = pch ^ ((r >> 1) & 7);
     const int oc = n0 + r;
-    if (oc < d.OC && !WSEG_DIAG_ZERO_B(d)) {
+    if (oc < d.OC) {
       bptr[i] = Wp + ((size_t)oc * a.taps * d.IC + (size_t)lch[i] * CH) * ES;
       b_inc[i] = ROWB;
     } else {
@@ -490,7 +482,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const Args a) {
         if (d.stride == 1) { iy = ty; ix = tx; }
         else { iy = ty / d.stride; ix = tx / d.stride; ok = ok && (iy * d.stride == ty) && (ix * d.stride == tx); }
       }
-      ok = ok && iy >= 0 && iy < a_H[i] && ix >= 0 && ix < a_W[i] && !WSEG_DIAG_ZERO_A(d);
+      ok = ok && iy >= 0 && iy < a_H[i] && ix >= 0 && ix < a_W[i];
       if (ok) {
         aptr[i] = IN + ((size_t)(a_img[i] + (long)iy * a_W[i] + ix) * d.ld_in + (size_t)lcha[i] * CH) * ES;
         a_inc[i] = ROWB;
@@ -1124,30 +1116,7 @@ __global__ __launch_bounds__(512, 2) void conv_bwd_pair_kernel(const Args ad, co
 
 }  // namespace
 
-static int conv_validate(const wseg_conv_desc* d) {
-  WSEG_CHECK(d && d->in && d->w && (d->out || d->out2), "conv_igemm: null pointer");
-  WSEG_CHECK(d->dtype == WSEG_F32 || d->dtype == WSEG_BF16 || d->dtype == WSEG_F32X3, "conv_igemm: bad dtype %d", d->dtype);
-  const int es = d->dtype == WSEG_BF16 ? 2 : 4;
-  WSEG_CHECK((d->IC * es) % ROWB == 0, "conv_igemm: IC=%d must be a multiple of %d", d->IC, ROWB / es);
-  WSEG_CHECK(d->OC % 8 == 0 && d->ld_in % 8 == 0, "conv_igemm: OC=%d / ld_in=%d must be multiples of 8", d->OC, d->ld_in);
-  WSEG_CHECK(d->N > 0 && d->OH > 0 && d->OW > 0 && d->IH > 0 && d->IW > 0, "conv_igemm: empty shape");
-  WSEG_CHECK(d->stride >= 1 && d->dil >= 1 && d->KH >= 1 && d->KW >= 1, "conv_igemm: bad geometry");
-  WSEG_CHECK(d->mode == 0 || d->mode == 1, "conv_igemm: bad mode");
-  WSEG_CHECK(d->epi >= 0 && d->epi <= 3, "conv_igemm: bad epilogue");
-  WSEG_CHECK(d->ld_in >= d->IC, "conv_igemm: ld_in < IC");
-  if (d->out) WSEG_CHECK(d->ld_out >= d->OC && d->ld_out % 8 == 0, "conv_igemm: bad ld_out");
-  if (d->out2) WSEG_CHECK(d->ld_out2 >= d->OC && d->ld_out2 % 8 == 0 && d->epi == 0, "conv_igemm: bad out2");
-  if (d->r_pre) WSEG_CHECK(d->ld_rpre % 8 == 0, "conv_igemm: bad ld_rpre");
-  if (d->r_post) WSEG_CHECK(d->ld_rpost % 8 == 0, "conv_igemm: bad ld_rpost");
-  if (d->mask) WSEG_CHECK(d->ld_mask % 8 == 0, "conv_igemm: bad ld_mask");
-  const long M = (long)d->N * d->OH * d->OW + (long)d->N * d->OH2 * d->OW2;
-  WSEG_CHECK(d->OH2 >= 0 && (d->OH2 == 0 || (d->OW2 > 0 && d->IH2 > 0 && d->IW2 > 0)), "conv_igemm: bad second segment");
-  WSEG_CHECK(d->w_rows == 0 || d->w_rows >= d->OC, "conv_igemm: w_rows=%d < OC=%d", d->w_rows, d->OC);
-  WSEG_CHECK(M < (1L << 31) && (long)d->N * d->IH * d->IW * d->ld_in < (1L << 40), "conv_igemm: tensor too large");
-  return 0;
-}
-
-// ---- host side ------------------------------------------------------------------------------------------------------------
+// ---- host side: one plan per launch (validate -> choose), then launch -------------------------------------------------------
 // Tile choice by CU time in units of (32 rows x 256 columns x K) at the 256-tile kernel's rate: a round of NI-block tiles costs NI, a round of the
 // 128^2 kernel (two resident workgroups of 2 units each, 0.75 of that rate) 5.33.  Fitted on the training AND the inference geometries
 // (scripts/bench_conv_infer.py).
@@ -1164,185 +1133,191 @@ static bool conv_rounds_prefer_224(long M, int ntn256) {
   return ((t7 + 255) / 256) * 7 < ((t8 + 255) / 256) * 8;
 }
 
-static long conv_rows(const wseg_conv_desc* d) { return (long)d->N * d->OH * d->OW + (long)d->N * d->OH2 * d->OW2; }
+// What one launch runs: the kernel family (WSEG_CONV_* of wseg_hip.h), its arguments, and for the 256-tile kernel its TAPF instantiation.
+struct ConvPlan { Args a; int family; bool tapf; };
 
-// The common part of every launch's arguments (K walk, two-source form).  < 0: error.
-static int conv_fill_args(const wseg_conv_desc* d, Args& a) {
+// Validate the descriptor, fill the arguments, choose the kernel.  wseg_conv_igemm, wseg_conv_bwd_pair and the plan queries all ask this function,
+// so the paired grid chooses exactly what the stand-alone launch would.  < 0: error (wseg_last_error), nothing may be launched.
+static int conv_plan(const wseg_conv_desc* d, ConvPlan& p) {
+  // -- validate
+  WSEG_CHECK(d && d->in && d->w && (d->out || d->out2), "conv_igemm: null pointer");
+  WSEG_CHECK(d->dtype == WSEG_F32 || d->dtype == WSEG_BF16 || d->dtype == WSEG_F32X3, "conv_igemm: bad dtype %d", d->dtype);
   const int es = d->dtype == WSEG_BF16 ? 2 : 4;
-  a.d = *d;
-  a.perm = 0; a.Q1 = a.Q2 = 0;
-  a.M = (int)conv_rows(d);
-  a.row0 = 0;
-  a.taps = d->KH * d->KW;
-  if (d->in2) {                                    // two sources: the second one is an extra last "tap" of w = [OC][KH*KW*IC + IC2]
+  WSEG_CHECK((d->IC * es) % ROWB == 0, "conv_igemm: IC=%d must be a multiple of %d", d->IC, ROWB / es);
+  WSEG_CHECK(d->OC % 8 == 0 && d->ld_in % 8 == 0, "conv_igemm: OC=%d / ld_in=%d must be multiples of 8", d->OC, d->ld_in);
+  WSEG_CHECK(d->N > 0 && d->OH > 0 && d->OW > 0 && d->IH > 0 && d->IW > 0, "conv_igemm: empty shape");
+  WSEG_CHECK(d->stride >= 1 && d->dil >= 1 && d->KH >= 1 && d->KW >= 1, "conv_igemm: bad geometry");
+  WSEG_CHECK(d->mode == 0 || d->mode == 1, "conv_igemm: bad mode");
+  WSEG_CHECK(d->epi >= 0 && d->epi <= 3, "conv_igemm: bad epilogue");
+  WSEG_CHECK(d->ld_in >= d->IC, "conv_igemm: ld_in < IC");
+  if (d->out) WSEG_CHECK(d->ld_out >= d->OC && d->ld_out % 8 == 0, "conv_igemm: bad ld_out");
+  if (d->out2) WSEG_CHECK(d->ld_out2 >= d->OC && d->ld_out2 % 8 == 0 && d->epi == 0, "conv_igemm: bad out2");
+  if (d->r_pre) WSEG_CHECK(d->ld_rpre % 8 == 0, "conv_igemm: bad ld_rpre");
+  if (d->r_post) WSEG_CHECK(d->ld_rpost % 8 == 0, "conv_igemm: bad ld_rpost");
+  if (d->mask) WSEG_CHECK(d->ld_mask % 8 == 0, "conv_igemm: bad ld_mask");
+  const long M = (long)d->N * d->OH * d->OW + (long)d->N * d->OH2 * d->OW2;                 // output rows (pixels) of both segments
+  const long in_rows = (long)d->N * d->IH * d->IW + (long)d->N * d->IH2 * d->IW2;
+  WSEG_CHECK(d->OH2 >= 0 && (d->OH2 == 0 || (d->OW2 > 0 && d->IH2 > 0 && d->IW2 > 0)), "conv_igemm: bad second segment");
+  WSEG_CHECK(d->w_rows == 0 || d->w_rows >= d->OC, "conv_igemm: w_rows=%d < OC=%d", d->w_rows, d->OC);
+  WSEG_CHECK(M < (1L << 31) && (long)d->N * d->IH * d->IW * d->ld_in < (1L << 40), "conv_igemm: tensor too large");
+  if (d->in2)                                      // two sources: the second one is an extra last "tap" of w = [OC][KH*KW*IC + IC2]
     WSEG_CHECK(d->KH == d->KW && (d->KH & 1) && d->KH * d->KW < 15 && d->stride == 1 && d->pad == d->dil * (d->KH / 2) &&
-               d->dtype == WSEG_BF16 && d->OC % 256 == 0 && d->ld_in2 % 8 == 0 && (d->bm_hint == 0 || d->bm_hint == 256 || d->bm_hint == 224),
+               d->dtype == WSEG_BF16 && d->OC % 256 == 0 && d->ld_in2 % 8 == 0 && d->epi != 3 && (d->bm_hint == 0 || d->bm_hint == 256 || d->bm_hint == 224),
                "conv_igemm: the two-source form is a same-size stride-1 bf16 convolution with OC %% 256 == 0 on the 256-tile kernel");
-    a.taps = d->KH * d->KW + 1;
-  }
-  a.cpt = d->IC * es / ROWB;
   const int ic2 = d->in2 ? (d->IC2 > 0 ? d->IC2 : d->IC) : 0;
   WSEG_CHECK(!d->in2 || ((ic2 * es) % ROWB == 0 && d->ld_in2 >= ic2), "conv_igemm: IC2=%d must be a multiple of %d and <= ld_in2", ic2, ROWB / es);
+  WSEG_CHECK(d->out || d->epi == 0, "conv_igemm: epilogue %d needs `out`", d->epi);
+  WSEG_CHECK(d->bm_hint != 257 && d->bm_hint != 258 && d->bm_hint >= 0, "conv_igemm: bm_hint %d was a development hook and no longer exists", d->bm_hint);
+
+  // -- the arguments every family shares (K walk, two-source form)
+  Args& a = p.a;
+  a.d = *d;
+  a.perm = 0; a.Q1 = a.Q2 = 0;
+  a.M = (int)M;
+  a.row0 = 0;
+  a.taps = d->KH * d->KW + (d->in2 ? 1 : 0);
+  a.cpt = d->IC * es / ROWB;
   a.cpt2 = ic2 * es / ROWB;
-  a.krow = d->in2 ? d->KH * d->KW * d->IC + ic2 : a.taps * d->IC;
+  a.krow = d->KH * d->KW * d->IC + ic2;
+  p.tapf = false;
+
+  // -- choose.  256 x 256 (or 224 x 256) phase-pipelined tiles: bf16 / split-bf16, whole 256-column tiles (OC % 256 != 0: only with a weight pack
+  // zero-padded to them, wseg_conv_desc.w_rows — the epilogue masks the columns >= OC); forced, two-source, or chosen by the CU-time model
+  const bool oc_ok = d->OC % 256 == 0 || (d->in2 == nullptr && d->w_rows >= ((d->OC + 255) / 256) * 256);
+  const bool can256 = (d->dtype == WSEG_BF16 || d->dtype == WSEG_F32X3) && oc_ok && d->epi != 3 && d->bm_hint != 64 && d->bm_hint != 128 &&
+                      d->bm_hint != 259 && d->KH <= 8 && d->KW <= 8 && a.taps <= 16;   // (tap list: 16 four-bit entries; tap masks: 8 + 8 bits)
+  if (can256 && (d->bm_hint == 256 || d->bm_hint == 224 || d->in2 != nullptr || conv_cost_prefers_256(M, d->OC))) {
+    WSEG_CHECK(d->IH <= 16384 && d->IW <= 16384 && d->OH <= 16384 && d->OW <= 16384 && d->pad <= 4096 && in_rows < (1L << 31),
+               "conv_igemm: shape too large for the 256-tile kernel");
+    if (d->mode == 1 && d->stride == 2 && d->OH % 2 == 0 && d->OW % 2 == 0 && d->OH2 % 2 == 0 && d->OW2 % 2 == 0 && a.taps <= 9 &&
+        (a.taps > 1 || d->bm_hint == 256)) {   // (1x1: nothing to skip in the K loop, the per-vector row mapping only costs — measured)
+      a.perm = 1;
+      a.Q1 = d->N * (d->OH / 2) * (d->OW / 2);
+      a.Q2 = d->N * (d->OH2 / 2) * (d->OW2 / 2);
+    }
+    a.ntn = (d->OC + 255) / 256;
+    const bool ni7 = d->bm_hint == 224 || (d->bm_hint == 0 && conv_rounds_prefer_224(M, a.ntn));
+    p.family = ni7 ? WSEG_CONV_224x256 : WSEG_CONV_256x256;
+    a.nwg = (int)(((M + (ni7 ? 223 : 255)) / (ni7 ? 224 : 256)) * a.ntn);
+    // the fast taps carry 32-bit byte offsets into the input(s) and no division (else: the full per-tap decode with 64-bit addresses, conv_igemm256_tile)
+    p.tapf = !(d->mode == 1 && d->stride != 1) && in_rows * std::max(d->ld_in, d->in2 ? d->ld_in2 : 0) * es < (1L << 31) - (1L << 24);
+    return 0;
+  }
+  // 512 x 128 phase-pipelined tiles for OC = 128 layers with many pixels (259 forces it); fast taps only
+  if (d->dtype == WSEG_BF16 && d->epi != 3 && d->OC % 128 == 0 && (d->mode == 0 || d->stride == 1) &&
+      (d->bm_hint == 259 || (d->bm_hint == 0 && d->OC == 128 && (M + 511) / 512 >= 512))) {
+    WSEG_CHECK(d->IH <= 8000 && d->IW <= 8000 && d->OH <= 8000 && d->OW <= 8000 && d->pad <= 4096 && d->KH * d->dil <= 4096,
+               "conv_igemm: shape too large for the 512x128-tile kernel");
+    p.family = WSEG_CONV_512x128;
+    a.ntn = d->OC / 128;
+    a.nwg = (int)(((M + 511) / 512) * a.ntn);
+    return 0;
+  }
+  // 128 x 128 tiles; few output pixels (view 2, 16x16 maps): 64-row tiles double the workgroup count.  (A split into full rounds of 128-row tiles +
+  // a short launch of 64-row tiles for the remainder was measured: no gain — workgroups are back-filled as they finish, rounds are not discrete.)
   a.ntn = (d->OC + BN - 1) / BN;
+  const bool small = d->bm_hint == 64 || (d->bm_hint != 128 && ((M + 127) / 128) * a.ntn < 384 && M > 64);
+  p.family = small ? WSEG_CONV_64x128 : WSEG_CONV_128x128;
+  a.nwg = (int)(((M + (small ? 63 : 127)) / (small ? 64 : 128)) * a.ntn);
   return 0;
 }
 
-// Does this launch run on the 256-tile kernel, and with which tile height?  ONE function for wseg_conv_igemm and for wseg_conv_bwd_pair (the paired
-// grid must choose exactly what the stand-alone launch would).  On return (true): a.ntn / a.nwg / a.perm / a.Q* are set for the 256-tile kernel.
-static bool conv_plan_256(const wseg_conv_desc* d, Args& a, bool& ni7) {
-  const long M = a.M;
-  ni7 = false;
-  // (OC % 256 != 0: only with a weight pack zero-padded to whole 256-row tiles, wseg_conv_desc.w_rows — the epilogue masks the columns >= OC)
-  const bool oc_ok = d->OC % 256 == 0 || (d->in2 == nullptr && d->w_rows >= ((d->OC + 255) / 256) * 256);
-  if (!((d->dtype == WSEG_BF16 || (d->dtype == WSEG_F32X3 && d->in2 == nullptr)) && oc_ok && d->epi != 3 && d->bm_hint != 64 && d->bm_hint != 128 &&
-        d->bm_hint != 259 && d->bm_hint >= 0 && d->KH <= 8 && d->KW <= 8 && a.taps <= 16))   // (tap list: 16 four-bit entries; tap masks: 8 + 8 bits)
-    return false;
-  static const int auto256 = getenv("WSEG_CONV256") ? atoi(getenv("WSEG_CONV256")) : 1;   // (0: A/B switch — 128-tile kernel everywhere)
-  if (!(d->bm_hint == 256 || d->bm_hint == 224 || d->in2 != nullptr || (auto256 && conv_cost_prefers_256(M, d->OC)))) return false;
-  if (!(d->IH <= 16384 && d->IW <= 16384 && d->OH <= 16384 && d->OW <= 16384 && d->pad <= 4096 &&
-        (long)d->N * d->IH * d->IW + (long)d->N * d->IH2 * d->IW2 < (1L << 31))) {
-    wseg_set_error("conv_igemm: shape too large for the 256-tile kernel");
-    a.nwg = -1;
-    return true;
+// the plan as the C ABI reports it (wseg_conv_plan, wseg_conv_bwd_pair_plan)
+static void conv_plan_report(const ConvPlan& p, wseg_launch_plan* out) {
+  static const int rows[] = {0, 64, 128, 224, 256, 512};
+  const bool t256 = p.family == WSEG_CONV_224x256 || p.family == WSEG_CONV_256x256;
+  *out = wseg_launch_plan{p.family, rows[p.family], t256 ? 256 : 128, p.a.nwg, p.a.perm, p.tapf, 0, 0};
+}
+
+static void conv_launch(const ConvPlan& p, hipStream_t s) {
+  const Args& a = p.a;
+  const dim3 grid(a.nwg);
+  switch (p.family) {
+    case WSEG_CONV_224x256:
+    case WSEG_CONV_256x256:
+      with_const<3>(a.d.epi, [&](auto epi) {
+        with_const<2>(p.family == WSEG_CONV_256x256, [&](auto ni8) {
+          with_const<2>(a.d.dtype == WSEG_F32X3, [&](auto x3) {
+            with_const<2>(p.tapf, [&](auto tapf) {
+              constexpr int DT = decltype(x3)::value ? WSEG_F32X3 : WSEG_BF16;
+              hipLaunchKernelGGL((conv_igemm256_kernel<decltype(epi)::value, 7 + decltype(ni8)::value, DT, decltype(tapf)::value != 0>), grid, dim3(512), 0, s, a);
+            });
+          });
+        });
+      });
+      break;
+    case WSEG_CONV_512x128:
+      with_const<3>(a.d.epi, [&](auto epi) { hipLaunchKernelGGL(conv_igemm512x128_kernel<decltype(epi)::value>, grid, dim3(512), 0, s, a); });
+      break;
+    default:
+      with_const<3>(a.d.dtype, [&](auto dt) {
+        with_const<4>(a.d.epi, [&](auto epi) {
+          with_const<2>(p.family == WSEG_CONV_128x128, [&](auto tall) {
+            hipLaunchKernelGGL((conv_igemm_kernel<decltype(dt)::value, decltype(epi)::value, decltype(tall)::value ? 128 : 64>), grid, dim3(256), 0, s, a);
+          });
+        });
+      });
   }
-  static const int perm_ok = getenv("WSEG_CONV_PERM") ? atoi(getenv("WSEG_CONV_PERM")) : 1;
-  if (perm_ok && d->mode == 1 && d->stride == 2 && d->OH % 2 == 0 && d->OW % 2 == 0 && d->OH2 % 2 == 0 && d->OW2 % 2 == 0 && a.taps <= 9 &&
-      (a.taps > 1 || d->bm_hint == 256)) {   // (1x1: nothing to skip in the K loop, the per-vector row mapping only costs — measured)
-    a.perm = 1;
-    a.Q1 = d->N * (d->OH / 2) * (d->OW / 2);
-    a.Q2 = d->N * (d->OH2 / 2) * (d->OW2 / 2);
-  }
-  a.ntn = (d->OC + 255) / 256;
-  static const int auto224 = getenv("WSEG_CONV224") ? atoi(getenv("WSEG_CONV224")) : 1;   // (0: A/B switch; 2: always)
-  ni7 = d->bm_hint != 256 && (d->bm_hint == 224 || (auto224 && d->bm_hint == 0 && (auto224 == 2 || conv_rounds_prefer_224(M, a.ntn))));
-  const int bmt = ni7 ? 224 : 256;
-  a.nwg = (int)(((M + bmt - 1) / bmt) * a.ntn);
-  return true;
+}
+
+extern "C" int wseg_conv_plan(const wseg_conv_desc* d, wseg_launch_plan* out) {
+  ConvPlan p;
+  WSEG_CHECK(out, "conv_plan: null output");
+  if (int rc = conv_plan(d, p)) return rc;
+  conv_plan_report(p, out);
+  return 0;
 }
 
 extern "C" int wseg_conv_igemm(const wseg_conv_desc* d, void* stream) {
-  if (int rc = conv_validate(d)) return rc;
-  const long M = conv_rows(d);
-  Args a;
-  if (int rc = conv_fill_args(d, a)) return rc;
-  // few output pixels (view 2, 16x16 maps): 64-row tiles double the workgroup count
-  const bool small = d->bm_hint == 64 || (d->bm_hint != 128 && ((M + 127) / 128) * a.ntn < 384 && M > 64);
-  hipStream_t s = (hipStream_t)stream;
-  WSEG_CHECK(d->out || d->epi == 0, "conv_igemm: epilogue %d needs `out`", d->epi);
-  WSEG_CHECK(d->bm_hint != 257 && d->bm_hint != 258 && d->bm_hint >= 0, "conv_igemm: bm_hint %d was a development hook and no longer exists", d->bm_hint);
-#define WSEG_LAUNCH_CONV1(DT_, EPI_, BM_) hipLaunchKernelGGL((conv_igemm_kernel<DT_, EPI_, BM_>), dim3(a.nwg), dim3(256), 0, s, a)
-#define WSEG_LAUNCH_CONV(BM_)                                                                                   \
-  do {                                                                                                          \
-    if (d->dtype == WSEG_BF16) {                                                                                \
-      if (d->epi == 0) WSEG_LAUNCH_CONV1(WSEG_BF16, 0, BM_); else if (d->epi == 1) WSEG_LAUNCH_CONV1(WSEG_BF16, 1, BM_); else if (d->epi == 2) WSEG_LAUNCH_CONV1(WSEG_BF16, 2, BM_); else WSEG_LAUNCH_CONV1(WSEG_BF16, 3, BM_); \
-    } else if (d->dtype == WSEG_F32X3) {                                                                        \
-      if (d->epi == 0) WSEG_LAUNCH_CONV1(WSEG_F32X3, 0, BM_); else if (d->epi == 1) WSEG_LAUNCH_CONV1(WSEG_F32X3, 1, BM_); else if (d->epi == 2) WSEG_LAUNCH_CONV1(WSEG_F32X3, 2, BM_); else WSEG_LAUNCH_CONV1(WSEG_F32X3, 3, BM_); \
-    } else {                                                                                                    \
-      if (d->epi == 0) WSEG_LAUNCH_CONV1(WSEG_F32, 0, BM_); else if (d->epi == 1) WSEG_LAUNCH_CONV1(WSEG_F32, 1, BM_); else if (d->epi == 2) WSEG_LAUNCH_CONV1(WSEG_F32, 2, BM_); else WSEG_LAUNCH_CONV1(WSEG_F32, 3, BM_); \
-    }                                                                                                           \
-  } while (0)
-  // 256 x 256 (or 224 x 256) phase-pipelined tiles: bf16 / split-bf16, OC % 256 == 0, chosen by the CU-time model
-  bool ni7 = false;
-  const bool big = conv_plan_256(d, a, ni7);
-  if (big && a.nwg < 0) return -1;
-  // 512 x 128 phase-pipelined tiles for OC = 128 layers with many pixels (259 forces it); fast taps only
-  static const int auto512 = getenv("WSEG_CONV512") ? atoi(getenv("WSEG_CONV512")) : 1;   // (0: A/B switch; measured 649 -> 766 TF/s on 128->128 3x3 224^2)
-  const bool tall = !big && d->dtype == WSEG_BF16 && d->epi != 3 && d->OC % 128 == 0 && (d->mode == 0 || d->stride == 1) &&
-                    (d->bm_hint == 259 || (auto512 && d->bm_hint == 0 && d->OC == 128 && (M + 511) / 512 >= 512));
-  if (tall) {
-    WSEG_CHECK(d->IH <= 8000 && d->IW <= 8000 && d->OH <= 8000 && d->OW <= 8000 && d->pad <= 4096 && d->KH * d->dil <= 4096,
-               "conv_igemm: shape too large for the 512x128-tile kernel");
-    a.ntn = d->OC / 128;
-    a.nwg = (int)(((M + 511) / 512) * a.ntn);
-    if (d->epi == 0) hipLaunchKernelGGL(conv_igemm512x128_kernel<0>, dim3(a.nwg), dim3(512), 0, s, a);
-    else if (d->epi == 1) hipLaunchKernelGGL(conv_igemm512x128_kernel<1>, dim3(a.nwg), dim3(512), 0, s, a);
-    else hipLaunchKernelGGL(conv_igemm512x128_kernel<2>, dim3(a.nwg), dim3(512), 0, s, a);
-    WSEG_LAUNCH_CHECK();
-    return 0;
-  }
-  if (big) {
-#define WSEG_LAUNCH_256(NI_, DT_, TF_)                                                                                         \
-  do {                                                                                                                         \
-    if (d->epi == 0) hipLaunchKernelGGL((conv_igemm256_kernel<0, NI_, DT_, TF_>), dim3(a.nwg), dim3(512), 0, s, a);             \
-    else if (d->epi == 1) hipLaunchKernelGGL((conv_igemm256_kernel<1, NI_, DT_, TF_>), dim3(a.nwg), dim3(512), 0, s, a);        \
-    else hipLaunchKernelGGL((conv_igemm256_kernel<2, NI_, DT_, TF_>), dim3(a.nwg), dim3(512), 0, s, a);                         \
-  } while (0)
-    const long es_ = d->dtype == WSEG_BF16 ? 2 : 4;
-    const long in_bytes = ((long)d->N * d->IH * d->IW + (long)d->N * d->IH2 * d->IW2) * std::max(d->ld_in, d->in2 ? d->ld_in2 : 0) * es_;
-    const bool tapf = !(d->mode == 1 && d->stride != 1) && in_bytes < (1L << 31) - (1L << 24);   // (else: the full per-tap decode with 64-bit addresses: conv_igemm256_tile)
-    if (d->dtype == WSEG_F32X3) {
-      if (tapf) { if (ni7) WSEG_LAUNCH_256(7, WSEG_F32X3, true); else WSEG_LAUNCH_256(8, WSEG_F32X3, true); }
-      else      { if (ni7) WSEG_LAUNCH_256(7, WSEG_F32X3, false); else WSEG_LAUNCH_256(8, WSEG_F32X3, false); }
-    } else {
-      if (tapf) { if (ni7) WSEG_LAUNCH_256(7, WSEG_BF16, true); else WSEG_LAUNCH_256(8, WSEG_BF16, true); }
-      else      { if (ni7) WSEG_LAUNCH_256(7, WSEG_BF16, false); else WSEG_LAUNCH_256(8, WSEG_BF16, false); }
-    }
-#undef WSEG_LAUNCH_256
-  } else if (small) {
-    a.nwg = (int)(((M + 63) / 64) * a.ntn);
-    WSEG_LAUNCH_CONV(64);
-  } else {
-    // (A split into full rounds of 128-row tiles + a short launch of 64-row tiles for the remainder was measured:
-    //  no gain — workgroups are back-filled as they finish, rounds are not discrete — so one launch it is.)
-    a.nwg = (int)(((M + 127) / 128) * a.ntn);
-    WSEG_LAUNCH_CONV(128);
-  }
-#undef WSEG_LAUNCH_CONV1
-#undef WSEG_LAUNCH_CONV
+  ConvPlan p;
+  if (int rc = conv_plan(d, p)) return rc;
+  conv_launch(p, (hipStream_t)stream);
   WSEG_LAUNCH_CHECK();
   return 0;
 }
 
-// One launch for `dg` (a stride-1 bf16 data gradient on the 256-tile kernel) and `wg` (a bf16 weight gradient on the 256 x 256 phase-pipelined
-// kernel) when both qualify; otherwise the two ordinary launches, in that order.  Results are those of the separate launches.
-// 1: the pair qualifies for the joint grid (a / ni7 / pl then hold both plans), 0: two launches, < 0: error
-static int conv_bwd_pair_plan(const wseg_conv_desc* dg, const wseg_wgrad_desc* wg, Args& a, bool& ni7, wseg_wg::Plan& pl) {
+// One launch for `dg` and `wg` when both plans qualify for the joint grid (see wseg_hip.h); otherwise the two ordinary launches, in that order.
+// 1: one grid (cp / wp hold both plans), 0: two launches (cp holds the first one's plan), < 0: error
+static int conv_bwd_pair_plan(const wseg_conv_desc* dg, const wseg_wgrad_desc* wg, ConvPlan& cp, wseg_wg::Plan& wp) {
   WSEG_CHECK(dg && wg, "conv_bwd_pair: null descriptor");
+  if (int rc = conv_plan(dg, cp)) return rc;
+  if (int rc = wseg_wg::wgrad_plan(wg, wp)) return rc;
   static const int pair_ok = getenv("WSEG_BWD_PAIR") ? atoi(getenv("WSEG_BWD_PAIR")) : 1;           // (0: A/B switch — two launches)
-  const bool cand = pair_ok && dg->dtype == WSEG_BF16 && wg->dtype == WSEG_BF16 && dg->mode == 1 && dg->stride == 1 && dg->bm_hint == 0 &&
-                    dg->out != nullptr && dg->out2 == nullptr && dg->epi >= 0 && dg->epi <= 2;
-  if (!cand) return 0;
-  if (((long)dg->N * dg->IH * dg->IW + (long)dg->N * dg->IH2 * dg->IW2) * std::max(dg->ld_in, dg->in2 ? dg->ld_in2 : 0) * 2L >= (1L << 31) - (1L << 24))
-    return 0;                                      // (the joint grid carries the 32-bit tap arithmetic only)
-  if (conv_validate(dg)) return 0;                 // (the fall-back launch reports the error)
-  {
-    // the two-source form errors out of conv_fill_args when it does not qualify: test its conditions first, quietly
-    const int ic2 = dg->in2 ? (dg->IC2 > 0 ? dg->IC2 : dg->IC) : 0;
-    if (dg->in2 && !(dg->KH == dg->KW && (dg->KH & 1) && dg->KH * dg->KW < 15 && dg->pad == dg->dil * (dg->KH / 2) && dg->OC % 256 == 0 &&
-                     dg->ld_in2 % 8 == 0 && ((ic2 * 2) % ROWB) == 0 && dg->ld_in2 >= ic2))
-      return 0;
-  }
-  if (conv_fill_args(dg, a)) return 0;
-  if (!conv_plan_256(dg, a, ni7) || a.nwg < 0 || a.perm) return 0;
-  if (int rc = wseg_wg::wgrad_plan(wg, pl)) return rc;
-  return pl.kind == 0 ? 1 : 0;
+  // (the joint grid carries the bf16 256-tile body with the 32-bit tap arithmetic in natural row order, writing `out` only)
+  return pair_ok && (cp.family == WSEG_CONV_224x256 || cp.family == WSEG_CONV_256x256) && cp.tapf && !cp.a.perm && dg->dtype == WSEG_BF16 &&
+         dg->mode == 1 && dg->bm_hint == 0 && dg->out2 == nullptr && wp.pipe;
 }
-extern "C" int wseg_conv_bwd_pair_fuses(const wseg_conv_desc* dg, const wseg_wgrad_desc* wg) {
-  wseg_wg::Plan pl; Args a; bool ni7;
-  return conv_bwd_pair_plan(dg, wg, a, ni7, pl);
+
+extern "C" int wseg_conv_bwd_pair_plan(const wseg_conv_desc* dg, const wseg_wgrad_desc* wg, wseg_launch_plan* dg_plan, wseg_launch_plan* wg_plan) {
+  ConvPlan cp; wseg_wg::Plan wp;
+  WSEG_CHECK(dg_plan && wg_plan, "conv_bwd_pair_plan: null output");
+  const int fuse = conv_bwd_pair_plan(dg, wg, cp, wp);
+  if (fuse < 0) return fuse;
+  conv_plan_report(cp, dg_plan);
+  wseg_wg::wgrad_plan_report(wp, wg_plan);
+  return fuse;
 }
 
 extern "C" int wseg_conv_bwd_pair(const wseg_conv_desc* dg, const wseg_wgrad_desc* wg, void* stream) {
-  wseg_wg::Plan pl; Args a; bool ni7 = false;
-  const int fuse = conv_bwd_pair_plan(dg, wg, a, ni7, pl);
+  ConvPlan cp; wseg_wg::Plan wp;
+  const int fuse = conv_bwd_pair_plan(dg, wg, cp, wp);
   if (fuse < 0) return fuse;
-  if (fuse != 1) {
-    if (int rc = wseg_conv_igemm(dg, stream)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (!fuse) {
+    conv_launch(cp, s);
+    WSEG_LAUNCH_CHECK();
     return wseg_conv_wgrad(wg, stream);
   }
+  const Args& a = cp.a;
   const int nd_pad = (a.nwg + 7) & ~7;
-  const dim3 grid((unsigned)(nd_pad + pl.a.nwg));
-  hipStream_t s = (hipStream_t)stream;
-#define WSEG_LAUNCH_PAIR(EPI_, NI_)                                                                                              \
-  do {                                                                                                                           \
-    if (pl.unit) hipLaunchKernelGGL((conv_bwd_pair_kernel<EPI_, NI_, 1>), grid, dim3(512), 0, s, a, pl.a, nd_pad);               \
-    else hipLaunchKernelGGL((conv_bwd_pair_kernel<EPI_, NI_, 0>), grid, dim3(512), 0, s, a, pl.a, nd_pad);                       \
-  } while (0)
-  if (ni7) { if (dg->epi == 0) WSEG_LAUNCH_PAIR(0, 7); else if (dg->epi == 1) WSEG_LAUNCH_PAIR(1, 7); else WSEG_LAUNCH_PAIR(2, 7); }
-  else { if (dg->epi == 0) WSEG_LAUNCH_PAIR(0, 8); else if (dg->epi == 1) WSEG_LAUNCH_PAIR(1, 8); else WSEG_LAUNCH_PAIR(2, 8); }
-#undef WSEG_LAUNCH_PAIR
+  const dim3 grid((unsigned)(nd_pad + wp.a.nwg));
+  with_const<3>(dg->epi, [&](auto epi) {
+    with_const<2>(cp.family == WSEG_CONV_256x256, [&](auto ni8) {
+      with_const<2>(wp.unit, [&](auto unit) {
+        hipLaunchKernelGGL((conv_bwd_pair_kernel<decltype(epi)::value, 7 + decltype(ni8)::value, decltype(unit)::value>), grid, dim3(512), 0, s, a, wp.a, nd_pad);
+      });
+    });
+  });
   WSEG_LAUNCH_CHECK();
   return 0;
 }

@@ -42,7 +42,7 @@ struct Args {
   int pix_per_split;
   int nsplit, nwg;
   int simple_adv, q64_1, r64_1, q64_2, r64_2;   // pipe kernel: 64 pixels = q*OW + r per row segment (simple_adv: one image wrap at most)
-  int wave_epi;      // pipe kernel: 1 = wave-local atomic epilogue (WSEG_WGRAD_EPI)
+  int wave_epi;      // pipe kernel: 1 = wave-local atomic epilogue (always; the block-wide branch is the follow-up of DESIGN.md §8)
   int diag;          // 0 = normal; timing diagnostics (WSEG_WGRAD_DIAG): 1 = no epilogue stores, 2 = plain stores, 4 / 5 = X / X and dY from the zero page
 };
 
@@ -648,7 +648,7 @@ __device__ __forceinline__ void conv_wgrad_pipe_tile(const Args& a, char* smem, 
   __syncthreads();                                 // every wave is done with the pipeline buffers
 
   if (a.wave_epi) {
-    // Epilogue, wave-local (default; WSEG_WGRAD_EPI=0 = the block-wide image below): every wave adds its own 128(oc) x 64(ic) accumulator tile to dW through
+    // Epilogue, wave-local (what every launch runs; wave_epi = 0 = the block-wide image below): every wave adds its own 128(oc) x 64(ic) accumulator tile to dW through
     // a private 16-row LDS scratch, no workgroup barrier; one atomic wave-instruction = 64 consecutive floats (256 B).
     constexpr int WLD = 64 + 4;
     float* wimg = reinterpret_cast<float*>(smem) + wid * (16 * WLD);
@@ -710,9 +710,9 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_pipe_kernel(const Args a) {
   conv_wgrad_pipe_tile<UNIT>(a, smem, blockIdx.x);
 }
 
-// host side: validation, tile geometry, split-K choice.  kind: 0 = 256x256 phase-pipelined kernel (bf16, big layers; `unit` picks its UNIT variant),
-// 1 = 256x256 plain, 2 = 128x128 (any dtype)
-struct Plan { Args a; int kind; bool unit; };
+// host side: validation, tile geometry, split-K choice.  pipe: the 256x256 phase-pipelined kernel (bf16, big layers; `unit` picks its UNIT variant),
+// else the 128x128 kernel (any dtype)
+struct Plan { Args a; bool pipe; bool unit; };
 static int wgrad_plan(const wseg_wgrad_desc* d, Plan& pl) {
   Args& a = pl.a;
   WSEG_CHECK(d && d->x && d->dy && d->dw, "conv_wgrad: null pointer");
@@ -769,15 +769,16 @@ static int wgrad_plan(const wseg_wgrad_desc* d, Plan& pl) {
 #else
   a.diag = 0;
 #endif
-  static const int wave_epi = getenv("WSEG_WGRAD_EPI") ? atoi(getenv("WSEG_WGRAD_EPI")) : 1;   // (same-box A/B: 12.64 vs 12.73 ms/step)
-  a.wave_epi = wave_epi;
-  static const bool use_pipe = !(getenv("WSEG_WGRAD_PIPE") && getenv("WSEG_WGRAD_PIPE")[0] == '0');
-  static const int unit_ok = getenv("WSEG_WGRAD_UNIT") ? atoi(getenv("WSEG_WGRAD_UNIT")) : 1;
-  pl.unit = unit_ok && a.simple_adv && d->stride == 1 && d->IH == d->OH && d->IW == d->OW &&
-            (d->OH2 == 0 || (d->IH2 == d->OH2 && d->IW2 == d->OW2));
-  pl.kind = (big && use_pipe) ? 0 : (big ? 1 : 2);
-  WSEG_CHECK(d->dw_rot == 0 || pl.kind == 2, "conv_wgrad: dw_rot is supported by the 128-tile kernel only");
+  a.wave_epi = 1;
+  pl.unit = a.simple_adv && d->stride == 1 && d->IH == d->OH && d->IW == d->OW && (d->OH2 == 0 || (d->IH2 == d->OH2 && d->IW2 == d->OW2));
+  pl.pipe = big;
+  WSEG_CHECK(d->dw_rot == 0 || !pl.pipe, "conv_wgrad: dw_rot is supported by the 128-tile kernel only");
   return 0;
+}
+// the plan as the C ABI reports it (wseg_wgrad_plan, wseg_conv_bwd_pair_plan)
+static void wgrad_plan_report(const Plan& pl, wseg_launch_plan* out) {
+  const int t = pl.pipe ? 256 : 128;
+  *out = wseg_launch_plan{pl.pipe ? WSEG_WGRAD_256x256 : WSEG_WGRAD_128x128, t, t, pl.a.nwg, 0, 0, pl.a.nsplit, pl.pipe && pl.unit};
 }
 }  // namespace
 }  // namespace wseg_wg

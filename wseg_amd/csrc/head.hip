@@ -162,15 +162,6 @@ __global__ void resize_planar_bwd_kernel(const float* __restrict__ d_out, float*
   if (accumulate) d_in[idx] += acc; else d_in[idx] = acc;
 }
 
-// ---- planar f32 [N][C][hw] <-> pixel rows [N*hw][ld] (cols c0..c0+C-1) in the mode dtype
-template <int DT>
-__global__ void planar_to_rows_kernel(const float* __restrict__ pl, void* __restrict__ rows, int ld, int c0, int C, int hw, long total) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const long n = idx / hw; const int p = (int)(idx - n * hw);
-  for (int c = 0; c < C; ++c) elem<DT>::st(rows, (size_t)idx * ld + c0 + c, pl[((size_t)n * C + c) * hw + p]);
-}
-
 // ---- d_head rows [N*hw][ld]: cols [0,128) = d_f_proj * (f_proj > 0), cols [128,149) = d_cam_low, rest 0
 template <int DT>
 __global__ void head_grad_rows_kernel(const float* __restrict__ d_fproj, const float* __restrict__ d_cam, const void* __restrict__ head,
@@ -241,15 +232,6 @@ extern "C" int wseg_resize_planar_bwd(const float* d_out, float* d_in, const flo
   WSEG_CHECK(d_out && d_in && planes > 0 && ih > 0 && iw > 0 && oh > 0 && ow > 0, "resize_planar_bwd: bad arguments");
   const long total = planes * ih * iw;
   hipLaunchKernelGGL(resize_planar_bwd_kernel, GRID1(total), 0, (hipStream_t)stream, d_out, d_in, plane_mul, plane_add, ih, iw, oh, ow, align, accumulate, total);
-  WSEG_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int wseg_planar_to_rows(const float* planar, void* rows, int ld, int c0, int C, int N, int hw, int dtype, void* stream) {
-  WSEG_CHECK(planar && rows && C > 0 && c0 >= 0 && c0 + C <= ld, "planar_to_rows: bad arguments");
-  const long total = (long)N * hw;
-  if (dtype == WSEG_BF16) hipLaunchKernelGGL(planar_to_rows_kernel<WSEG_BF16>, GRID1(total), 0, (hipStream_t)stream, planar, rows, ld, c0, C, hw, total);
-  else hipLaunchKernelGGL(planar_to_rows_kernel<WSEG_F32>, GRID1(total), 0, (hipStream_t)stream, planar, rows, ld, c0, C, hw, total);
   WSEG_LAUNCH_CHECK();
   return 0;
 }

@@ -99,20 +99,6 @@ __global__ void cls_loss_kernel(const float* __restrict__ stats, const float* __
   if (threadIdx.x == 0) atomicAdd(loss_out, tot / (20.f * N));
 }
 
-// ---- adaptive min-pooling values (contrast_train.py:16-22): q = max_{c>=1} U[n,c,p]*L[n,c], arg channel
-__global__ void rvmin_values_kernel(const float* __restrict__ U, const float* __restrict__ label20, float* __restrict__ q,
-                                    unsigned char* __restrict__ argc, int npix, long total) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const long n = idx / npix; const int p = (int)(idx - n * npix);
-  float best = -INFINITY; int bc = 1;
-  for (int c = 1; c < 21; ++c) {
-    const float v = U[((size_t)n * 21 + c) * npix + p] * label20[n * 20 + c - 1];
-    if (v > best) { best = v; bc = c; }
-  }
-  q[idx] = best; argc[idx] = (unsigned char)bc;
-}
-
 // ---- radix select of the k-th order statistic per row (values as order-preserving uint keys)
 __device__ __forceinline__ unsigned f2key(float f) { unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 __device__ __forceinline__ float key2f(unsigned k) { unsigned u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k; return __uint_as_float(u); }
@@ -224,94 +210,6 @@ __global__ void select_finish_kernel(const float* __restrict__ res, int rows, in
       t += res[r * 4 + 1] + ((float)k - res[r * 4 + 2]) * thr;
     }
     atomicAdd(loss_out, t * scale);
-  }
-}
-
-// ---- rvmin backward: pixels among the k smallest with q > 0 send coef*L to their arg channel
-__global__ void rvmin_bwd_kernel(const float* __restrict__ q, const unsigned char* __restrict__ argc, const float* __restrict__ res,
-                                 const float* __restrict__ label20, float* __restrict__ dU, int npix, int k, float coef, long total) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const long n = idx / npix; const int p = (int)(idx - n * npix);
-  const float v = q[idx], thr = res[n * 4 + 0];
-  float w = 0.f;
-  if (v < thr) w = 1.f;
-  else if (v == thr) { const float ce = res[n * 4 + 3]; w = ce > 0.f ? ((float)k - res[n * 4 + 2]) / ce : 0.f; }
-  if (w > 0.f && v > 0.f) {
-    const int c = argc[idx];
-    dU[((size_t)n * 21 + c) * npix + p] += w * coef * label20[n * 20 + c - 1];
-  }
-}
-
-// ---- out[n,c,P] = L * resize_{S->OS}( relu(relu(U) - mn - e) / (mx - mn + e) )      (visualization.py:62-67 + :145-158)
-__global__ void norm_resize_fwd_kernel(const float* __restrict__ U, const float* __restrict__ stats, const float* __restrict__ label20,
-                                       float* __restrict__ out, int S, int OS, long total) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const int ox = (int)(idx % OS); const long r = idx / OS;
-  const int oy = (int)(r % OS); const long pl = r / OS;
-  const int c = (int)(pl % 21); const long n = pl / 21;
-  const float L = c == 0 ? 1.f : label20[n * 20 + c - 1];
-  float v = 0.f;
-  if (L != 0.f) {
-    const float mx = stats[pl * 6 + 0], mn = stats[pl * 6 + 1];
-    const float invD = 1.f / (mx - mn + 1e-5f);
-    int y0, y1, x0, x1; float fy, fx;
-    const float sc = ac_scale(S, OS);
-    src_index(oy, sc, S, y0, y1, fy); src_index(ox, sc, S, x0, x1, fx);
-    const float* p = U + (size_t)pl * S * S;
-    auto f = [&](int y, int x) { return fmaxf(fmaxf(p[(size_t)y * S + x], 0.f) - mn - 1e-5f, 0.f) * invD; };
-    v = (1.f - fy) * ((1.f - fx) * f(y0, x0) + fx * f(y0, x1)) + fy * ((1.f - fx) * f(y1, x0) + fx * f(y1, x1));
-    v *= L;
-  }
-  out[idx] = v;
-}
-
-// backward of the above; one workgroup per plane: scatters into dU and routes the max/min gradients
-__global__ __launch_bounds__(256) void norm_resize_bwd_kernel(const float* __restrict__ G, const float* __restrict__ U, const float* __restrict__ stats,
-                                                              const float* __restrict__ label20, float* __restrict__ dU, int S, int OS) {
-  __shared__ float red[4];
-  const int pl = blockIdx.x;
-  const int c = pl % 21; const int n = pl / 21;
-  const float L = c == 0 ? 1.f : label20[n * 20 + c - 1];
-  if (L == 0.f) return;
-  const float mx = stats[(size_t)pl * 6 + 0], mn = stats[(size_t)pl * 6 + 1];
-  const float invD = 1.f / (mx - mn + 1e-5f);
-  const float sc = ac_scale(S, OS);
-  const float* p = U + (size_t)pl * S * S;
-  float* dp = dU + (size_t)pl * S * S;
-  const float* g = G + (size_t)pl * OS * OS;
-  float A = 0.f, B = 0.f;
-  for (int o = threadIdx.x; o < OS * OS; o += 256) {
-    const float go = g[o] * L;
-    if (go == 0.f) continue;
-    const int oy = o / OS, ox = o - oy * OS;
-    int y0, y1, x0, x1; float fy, fx;
-    src_index(oy, sc, S, y0, y1, fy); src_index(ox, sc, S, x0, x1, fx);
-    const int ys[2] = {y0, y1}, xs[2] = {x0, x1};
-    const float wy[2] = {1.f - fy, fy}, wx[2] = {1.f - fx, fx};
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const float w = wy[a] * wx[b];
-        if (w == 0.f) continue;
-        const size_t qi = (size_t)ys[a] * S + xs[b];
-        const float u = p[qi];
-        const float av = fmaxf(fmaxf(u, 0.f) - mn - 1e-5f, 0.f);
-        if (av > 0.f) {                                   // implies u > 0
-          const float t = go * w * invD;
-          atomicAdd(&dp[qi], t);
-          B += t;
-          A += t * av * invD;
-        }
-      }
-  }
-  const float At = block_sum(A, red), Bt = block_sum(B, red);
-  if (threadIdx.x == 0) {
-    const int imx = __float_as_int(stats[(size_t)pl * 6 + 3]), imn = __float_as_int(stats[(size_t)pl * 6 + 4]);
-    if (p[imx] > 0.f) atomicAdd(&dp[imx], -At);          // d/d mx
-    if (p[imn] > 0.f) atomicAdd(&dp[imn], At - Bt);      // d/d mn
   }
 }
 
@@ -1289,14 +1187,6 @@ extern "C" int wseg_cls_loss(const float* stats, const float* label20, float* lo
   return 0;
 }
 
-extern "C" int wseg_rvmin_values(const float* U, const float* label20, float* q, unsigned char* argc, int N, int npix, void* stream) {
-  WSEG_CHECK(U && label20 && q && argc && N > 0 && npix > 0, "rvmin_values: bad arguments");
-  const long total = (long)N * npix;
-  hipLaunchKernelGGL(rvmin_values_kernel, GRID1(total), 0, ST, U, label20, q, argc, npix, total);
-  WSEG_LAUNCH_CHECK();
-  return 0;
-}
-
 // k-th order statistic per row + partial sums.  largest=1: the k largest; res[row] = {thr, sum_strict, cnt_strict, cnt_tie}
 // workspace: unsigned state[rows*4] + unsigned hist[rows*256]  (wseg_select_workspace_bytes)
 extern "C" size_t wseg_select_workspace_bytes(int rows) { return (size_t)rows * (4 + 256) * sizeof(unsigned); }
@@ -1335,29 +1225,6 @@ static __global__ void loss_finish_kernel(const float* __restrict__ acc, float e
 extern "C" int wseg_loss_finish(const float* acc, float er_coef, float* out8, void* stream) {
   WSEG_CHECK(acc && out8, "loss_finish: bad arguments");
   hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(64), 0, ST, acc, er_coef, out8);
-  WSEG_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int wseg_rvmin_backward(const float* q, const unsigned char* argc, const float* res, const float* label20, float* dU,
-                                   int N, int npix, int k, float coef, void* stream) {
-  WSEG_CHECK(q && argc && res && label20 && dU, "rvmin_backward: bad arguments");
-  const long total = (long)N * npix;
-  hipLaunchKernelGGL(rvmin_bwd_kernel, GRID1(total), 0, ST, q, argc, res, label20, dU, npix, k, coef, total);
-  WSEG_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int wseg_norm_resize_forward(const float* U, const float* stats, const float* label20, float* out, int N, int S, int OS, void* stream) {
-  WSEG_CHECK(U && stats && label20 && out && N > 0 && S > 0 && OS > 0, "norm_resize_forward: bad arguments");
-  const long total = (long)N * 21 * OS * OS;
-  hipLaunchKernelGGL(norm_resize_fwd_kernel, GRID1(total), 0, ST, U, stats, label20, out, S, OS, total);
-  WSEG_LAUNCH_CHECK();
-  return 0;
-}
-extern "C" int wseg_norm_resize_backward(const float* G, const float* U, const float* stats, const float* label20, float* dU, int N, int S, int OS, void* stream) {
-  WSEG_CHECK(G && U && stats && label20 && dU && N > 0, "norm_resize_backward: bad arguments");
-  hipLaunchKernelGGL(norm_resize_bwd_kernel, dim3(N * 21), dim3(256), 0, ST, G, U, stats, label20, dU, S, OS);
   WSEG_LAUNCH_CHECK();
   return 0;
 }
