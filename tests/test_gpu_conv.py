@@ -52,6 +52,7 @@ CASES = [
     (1, 9, 9, 256, 24, 1, 1, 1),
     (1, 13, 11, 256, 512, 3, 1, 2),      # 256x256-tile wgrad path (bf16), odd spatial size
     (2, 10, 10, 320, 256, 1, 1, 1),      # 256-tile path with an IC tail
+    (2, 10, 10, 320, 320, 3, 1, 1),      # 256-tile wgrad (same-size 3x3) with a 64-wide tail in both tile dimensions; 200 pixels = 3 full K-tiles + 1 partial
 ]
 
 
@@ -113,6 +114,31 @@ def test_conv_fwd_dgrad_wgrad(case, dt, bm):
     # split-K path + accumulation on top of existing content
     L.conv_wgrad(xg, dyg, dwg, N=N, IH=H, IW=W, IC=IC, OH=OH, OW=OW, OC=OC, KH=k, KW=k, stride=s, dil=d, pad=pad, split_k=3, dtype=cdt)
     assert np.abs(dwg.cpu().numpy() - 2 * ref).max() / scale < 2 * wtol
+
+
+@pytest.mark.parametrize("tile_hint", [128, 256])
+def test_wgrad_dw_extents(tile_hint):
+    """A dw narrower than the operands (IC_dw < IC, OC_dw < OC) on either weight-gradient kernel: the epilogue adds exactly the [OC_dw][taps][IC_dw]
+    block, twice on top of zeros, and writes nothing behind it (a sentinel guard follows the buffer)."""
+    N, H, W, C, k = 2, 12, 10, 256, 3
+    IC_dw, OC_dw, GUARD, SENTINEL = 248, 200, 4096, -12345.0
+    tdt, dev = torch.bfloat16, "cuda"
+    x = _rand((N, C, H, W), 1).to(tdt).float()
+    w = _rand((C, C, k, k), 2, (2.0 / (C * k * k)) ** 0.5).to(tdt).float().requires_grad_(True)
+    dy = _rand((N, C, H, W), 3).to(tdt).float()
+    F.conv2d(x, w, None, 1, 1, 1).backward(dy)
+    ref = w.grad.permute(0, 2, 3, 1).reshape(C, k * k, C).numpy()
+    xg, dyg = _nhwc(x).to(dev, tdt), _nhwc(dy).to(dev, tdt)
+    n = OC_dw * k * k * IC_dw
+    buf = torch.zeros(n + GUARD, device=dev, dtype=torch.float32)
+    buf[n:] = SENTINEL
+    for _ in range(2):
+        _wgrad(WGRAD_PIPE if tile_hint == 256 else WGRAD_128, xg, dyg, buf, N=N, IH=H, IW=W, IC=C, OH=H, OW=W, OC=C, KH=k, KW=k, pad=1,
+               IC_dw=IC_dw, OC_dw=OC_dw, split_k=2, tile_hint=tile_hint)
+    got = buf.cpu().numpy()
+    dw = got[:n].reshape(OC_dw, k * k, IC_dw)
+    assert np.abs(dw - 2 * ref[:OC_dw, :, :IC_dw]).max() / np.abs(ref).max() < 2 * 1e-2
+    assert np.array_equal(got[n:].view(np.uint32), np.full(GUARD, SENTINEL, dtype=np.float32).view(np.uint32))
 
 
 @pytest.mark.parametrize("dt,OC,bm", [("f32", 128, 0), ("bf16", 128, 0), ("bf16", 256, 256), ("bf16", 256, 224), ("bf16", 128, 259)])

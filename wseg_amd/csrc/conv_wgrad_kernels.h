@@ -42,9 +42,40 @@ struct Args {
   int pix_per_split;
   int nsplit, nwg;
   int simple_adv, q64_1, r64_1, q64_2, r64_2;   // pipe kernel: 64 pixels = q*OW + r per row segment (simple_adv: one image wrap at most)
-  int wave_epi;      // pipe kernel: 1 = wave-local atomic epilogue (always; the block-wide branch is the follow-up of DESIGN.md §8)
-  int diag;          // 0 = normal; timing diagnostics (WSEG_WGRAD_DIAG): 1 = no epilogue stores, 2 = plain stores, 4 / 5 = X / X and dY from the zero page
+  int diag;          // 0 = normal; pipe kernel timing diagnostics (WSEG_WGRAD_DIAG, probe builds): 4 / 5 = X / X and dY from the zero page, 6 = no LDS-DMA request inside the loop
 };
+
+// bf16 LDS tiles: the XOR swizzle s(pix) of the 32-B blocks of pixel row `row` (see the header comment)
+__device__ __forceinline__ constexpr int swz32(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
+
+// What one workgroup computes: the BO x BI block (oc0, ic0) of tap (ky, kx), reduced over the pixels [m_begin, m_end) of its split.
+struct WgTile { int tile, split, tap, ky, kx, oc0, ic0, m_begin, m_end; };
+
+// block -> (tile, pixel split).  All tiles of one split read the same dY / X rows: keep them on ONE XCD
+// (blocks b and b+8 share an XCD) so the rows are fetched into that XCD's L2 once and every other tile's
+// LDS-DMA hits L2 (~70 GB/s per CU) instead of MALL/HBM (~25-33 GB/s per CU).
+template <int BO, int BI>
+__device__ __forceinline__ WgTile wg_tile_of(const Args& a, const int bid) {
+  WgTile t;
+  if ((a.nsplit & 7) == 0) {
+    const int xcd = bid & 7, j = bid >> 3, q = a.nsplit >> 3;
+    t.tile = j % a.ntiles;
+    t.split = xcd * q + j / a.ntiles;
+  } else {
+    const int l = xcd_remap(bid, a.nwg);                  // contiguous logical ids per XCD: the taps of an (oc,ic) tile pair
+    t.tile = l % a.ntiles;
+    t.split = l / a.ntiles;
+  }
+  t.tap = t.tile % a.taps;
+  const int t2 = t.tile / a.taps;
+  t.oc0 = t2 / a.nti * BO;
+  t.ic0 = t2 % a.nti * BI;
+  t.ky = t.tap / a.d.KW;
+  t.kx = t.tap - t.ky * a.d.KW;
+  t.m_begin = t.split * a.pix_per_split;
+  t.m_end = min(a.M, t.m_begin + a.pix_per_split);
+  return t;
+}
 
 template <int DT, int BO, int BI, int WR, int WC>
 __global__ __launch_bounds__(WR * WC * 64, 2) void conv_wgrad_kernel(const Args a) {
@@ -68,26 +99,8 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void conv_wgrad_kernel(const Args 
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // block -> (tile, pixel split).  All tiles of one split read the same dY / X rows: keep them on ONE XCD
-  // (blocks b and b+8 share an XCD) so the rows are fetched into that XCD's L2 once and every other tile's
-  // LDS-DMA hits L2 (~70 GB/s per CU) instead of MALL/HBM (~25-33 GB/s per CU).
-  int tile, split;
-  if ((a.nsplit & 7) == 0) {
-    const int b = blockIdx.x, xcd = b & 7, j = b >> 3, q = a.nsplit >> 3;
-    tile = j % a.ntiles;
-    split = xcd * q + j / a.ntiles;
-  } else {
-    const int l = xcd_remap(blockIdx.x, a.nwg);           // contiguous logical ids per XCD: the taps of an (oc,ic) tile pair
-    tile = l % a.ntiles;
-    split = l / a.ntiles;
-  }
-  const int tap = tile % a.taps;
-  const int t2 = tile / a.taps;
-  const int ti = t2 % a.nti, to = t2 / a.nti;
-  const int oc0 = to * BO, ic0 = ti * BI;
-  const int ky = tap / d.KW, kx = tap - ky * d.KW;
-  const int m_begin = split * a.pix_per_split;
-  const int m_end = min(a.M, m_begin + a.pix_per_split);
+  const WgTile wt = wg_tile_of<BO, BI>(a, blockIdx.x);
+  const int tap = wt.tap, ky = wt.ky, kx = wt.kx, oc0 = wt.oc0, ic0 = wt.ic0, m_begin = wt.m_begin, m_end = wt.m_end;
   if (m_begin >= m_end) return;
 
   const char* zero = reinterpret_cast<const char*>(g_wseg_zero_page);
@@ -97,7 +110,7 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void conv_wgrad_kernel(const Args 
   // logical 16-B chunk fetched into physical chunk `pch` of pixel row r (rows are ROWB bytes)
   auto logical_chunk = [](int r, int pch) {
     if constexpr (DT == WSEG_BF16) {
-      const int s = (r & 3) | (((r >> 3) & 1) << 2);
+      const int s = swz32(r);
       const int blk = pch >> 1;                                   // 32-B block
       return ((((blk & ~7) | ((blk ^ s) & 7))) << 1) | (pch & 1);
     } else {
@@ -199,7 +212,7 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void conv_wgrad_kernel(const Args 
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const int row = ks * 32 + fk * 8 + h * 4 + q;
-          const int s = (row & 3) | (((row >> 3) & 1) << 2);
+          const int s = swz32(row);
 #pragma unroll
           for (int i = 0; i < MI; ++i) {
             const int blk = wr * MI + i;
@@ -318,145 +331,82 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void conv_wgrad_kernel(const Args 
   }
 }
 
-// ---- 256x256 bf16 phase-pipelined variant (the schedule validated in csrc/gemm256_probe.hip: 1.1-1.2 PF on
-// plain GEMM).  K-tile = 64 pixels; LDS = 2 K-tiles x 4 half-tile slots {dY ch 0-127, dY ch 128-255, X ch 0-127,
-// X ch 128-255}, each [64 pixels][128 ch] = 16 KiB.  A K-tile is 4 phases of 16 MFMAs (one 64(oc) x 32(ic)
-// quadrant of the wave's 128 x 64 tile); each phase refills ONE slot every wave has finished reading:
-//     p1(u): dY0(u+1)   p2(u): dY1(u+1)   p3(u): X0(u+2)   p4(u): X1(u+2)
-// and the only DMA wait is a counted s_waitcnt vmcnt(4) in p4.  One raw s_barrier per phase.  The transposed
-// fragment reads go through inline asm (hipcc would put vmcnt(0) in front of ds_read_tr builtins while
-// LDS-DMA is in flight), with an explicit lgkmcnt(0) + sched_barrier before the MFMAs.
-template <int UNIT>
-                                 // UNIT 1: stride 1 and IH==OH, IW==OW in both segments (the X source row is m + const)
-__device__ __forceinline__ void conv_wgrad_pipe_tile(const Args& a, char* smem, const int bid) {   // (smem: the workgroup's 128 KiB LDS buffer)
-  constexpr int BO = 256, BI = 256, NT = 512;
-  constexpr int PK = 64, HALF = 16384, TILE = 4 * HALF, ROWB = 256;
-  constexpr int EPI_ROWS = 64, EPI_LD = BI + 4;
-  const wseg_wgrad_desc& d = a.d;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int tile, split;
-  if ((a.nsplit & 7) == 0) {
-    const int b = bid, xcd = b & 7, j = b >> 3, q8 = a.nsplit >> 3;
-    tile = j % a.ntiles; split = xcd * q8 + j / a.ntiles;
-  } else {
-    const int l = xcd_remap(bid, a.nwg);
-    tile = l % a.ntiles; split = l / a.ntiles;
-  }
-  const int tap = tile % a.taps;
-  const int t2 = tile / a.taps;
-  const int ti = t2 % a.nti, to = t2 / a.nti;
-  const int oc0 = to * BO, ic0 = ti * BI;
-  const int ky = tap / d.KW, kx = tap - ky * d.KW;
-  const int m_begin = split * a.pix_per_split;
-  const int m_end = min(a.M, m_begin + a.pix_per_split);
-  if (m_begin >= m_end) return;
-  const char* zero = reinterpret_cast<const char*>(g_wseg_zero_page);
-  const char* X = reinterpret_cast<const char*>(d.x);
-  const char* DY = reinterpret_cast<const char*>(d.dy);
+// ---- Operand staging of the 256x256 pipe kernel (conv_wgrad_pipe_tile below).  A K-tile is 64 pixel rows of dY and of X, each as two
+// half-tiles [64 pixels][128 channels] = 16 KiB; thread -> rows r0 = tid>>4 and r0+32 of every half-tile, physical 16-B chunk tid&15, one
+// LDS-DMA request per row.  Two stagers with one interface, chosen by the geometry (StageUnit / StageGeneral):
+//     issue_y(h, buf)   channel half h of the NEXT dY tile into buffer buf; h == 1 advances to the following tile
+//     prepare_x()       once per X tile, before its two issue_x: where its rows come from; advances the coordinates to the next tile
+//     issue_x(h, buf)   channel half h of the prepared X tile
+//     ntiles()          K-tiles of the workgroup's pixel range
+// All per-K-tile address work is INCREMENTAL (the K loop is VALU-sensitive: 64 MFMAs per wave per K-tile leave ~250 issue slots):
+// dY pointers advance by a constant; the X pixel coordinates (n, oy, ox) advance by 64 rows with one add / compare / subtract each
+// instead of three integer divisions per row.
+struct StageBase {
+  static constexpr int PK = 64, HALF = 16384;
+  const Args& a;
+  const wseg_wgrad_desc& d;
+  const WgTile& t;
+  char* const smem;
+  const int tid, wid;
+  const char* zsrc;                                  // this lane's 16 B of the zero page (rows outside the range, padded taps, absent channels)
+  int lc[2];                                         // logical (unswizzled) 16-B chunk of row k = 0, 1
+  const char* ybase[2];                              // dY source of the NEXT Y tile (row k, chunk lc[k], half 0)
+  size_t ystep;                                      // 64 rows of dY
 
-  // LDS slot (buffer buf, half-tile which = dY0, dY1, X0, X1).  The 2-phase schedules interleave the two buffers at slot
-  // granularity so that the buffer offset fits the ds_read immediate (all transposed reads then need no address VALU).
-  auto slot_off = [](int buf, int which) { return (which * 2 + buf) * HALF; };
-  // staging: thread -> rows r0 = tid>>4 and r0+32 of every half-tile, physical 16-B chunk tid&15.
-  // All per-K-tile address work is INCREMENTAL (this loop is VALU-sensitive: 64 MFMAs per wave per K-tile leave
-  // ~250 issue slots): dY pointers advance by a constant; the X pixel coordinates (n, oy, ox) advance by 64 rows
-  // with one add / compare / subtract each instead of three integer divisions per row.
-  const int pch = tid & 15;
-  const char* zsrc = zero + (lane & 15) * 16;
-  int lc[2];
-  const char* ybase[2];                              // dY source of the NEXT Y tile (row rr[k], chunk lc[k], half 0)
-  int my[2];                                         // its pixel row
-  int xm[2], xoy[2], xox[2], xbase[2];               // NEXT X tile: pixel row, output coordinates, first input row of the image
-  const int M1 = d.N * d.OH * d.OW;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int rr = (tid >> 4) + 32 * k;
-    const int sw = (rr & 3) | (((rr >> 3) & 1) << 2);
-    lc[k] = (((pch >> 1) ^ sw) << 1) | (pch & 1);
-    my[k] = m_begin + rr;
-    ybase[k] = DY + ((size_t)my[k] * d.ld_dy + oc0 + lc[k] * 8) * 2;
-    xm[k] = m_begin + rr;
-    const wseg_rowgeo rg = wseg_decode_row(d, min(xm[k], a.M - 1));
-    xoy[k] = rg.oy; xox[k] = rg.ox; xbase[k] = (int)rg.in_base;
-  }
-  const size_t ystep = (size_t)PK * d.ld_dy * 2;
-  const bool yok[2][2] = {{oc0 + lc[0] * 8 < d.OC, oc0 + 128 + lc[0] * 8 < d.OC}, {oc0 + lc[1] * 8 < d.OC, oc0 + 128 + lc[1] * 8 < d.OC}};
-  const bool xok[2][2] = {{ic0 + lc[0] * 8 < d.IC, ic0 + 128 + lc[0] * 8 < d.IC}, {ic0 + lc[1] * 8 < d.IC, ic0 + 128 + lc[1] * 8 < d.IC}};
-  const char* xrow[2];                               // source pixel row (chunk lc[k], half 0) of the X tile being issued, or nullptr
-  // UNIT geometry: input pixel of (output row m, tap) = m + dy*W + dx inside its segment, so the source pointer is a running
-  // pointer (+64 rows per K-tile, + a constant when crossing into the second segment) and only the VALIDITY needs (oy, ox).
-  const int dy = ky * d.dil - d.pad, dx = kx * d.dil - d.pad;
-  const char* xptr[2];
-  if constexpr (UNIT) {
+  __device__ __forceinline__ StageBase(const Args& a_, const WgTile& t_, char* smem_, int tid_, int wid_)
+      : a(a_), d(a_.d), t(t_), smem(smem_), tid(tid_), wid(wid_) {
+    zsrc = reinterpret_cast<const char*>(g_wseg_zero_page) + (tid & 15) * 16;
+    const int pch = tid & 15;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-      const bool s2 = d.OH2 != 0 && m_begin >= M1;   // the workgroup's FIRST segment (uniform); the switch adds xcross
-      const long shift = (long)dy * (s2 ? d.IW2 : d.IW) + dx;
-      xptr[k] = X + (((long)xm[k] + shift) * d.ld_x + ic0 + lc[k] * 8) * 2;
+      lc[k] = (((pch >> 1) ^ swz32(row(k))) << 1) | (pch & 1);
+      ybase[k] = reinterpret_cast<const char*>(d.dy) + ((size_t)(t.m_begin + row(k)) * d.ld_dy + t.oc0 + lc[k] * 8) * 2;
     }
+    ystep = (size_t)PK * d.ld_dy * 2;
   }
-  const size_t xstep = (size_t)PK * d.ld_x * 2;
-  const long xcross = (long)dy * (d.IW2 - d.IW) * d.ld_x * 2;      // pointer correction when a row enters segment 2
-  // UNIT: the K-tiles never straddle the boundary between the two row segments (views): the pixel range is walked as
-  // [m_begin, min(m_end, M1)) then [max(m_begin, M1), m_end), each in 64-row tiles (at most one tile more than a straight walk;
-  // rows past a sub-range's end read the zero page on both operands).  All geometry of a tile is then wave-uniform (scalars):
-  // per row there remain two bounds tests, the (oy, ox) advance and the source select — this loop is VALU-sensitive.
-  const int seg_end = d.OH2 != 0 ? M1 : a.M;
-  const int a_end = min(m_end, seg_end), b_begin = max(m_begin, seg_end);
-  const int nA = m_begin < a_end ? (a_end - m_begin + PK - 1) / PK : 0;
-  const int nB = m_end > b_begin ? (m_end - b_begin + PK - 1) / PK : 0;
-  int ty_idx = 0, tx_idx = 0;                        // index of the NEXT dY / X tile to issue
-  int y_m = m_begin, x_m = m_begin;                  // its first pixel row
-  int y_lim = nA > 0 ? a_end : m_end, x_lim = y_lim; // end of its sub-range
-  bool x_s2 = nA == 0 && d.OH2 != 0;                 // the X tile's segment
-  int rry[2][2], rrx[2][2];                          // row inside the tile per (k, h); huge where the channel half does not exist
-  bool xin[2] = {false, false};                      // the X tile being issued: tap lands inside the image
-  if constexpr (UNIT) {
+  __device__ __forceinline__ int row(int k) const { return (tid >> 4) + 32 * k; }   // the thread's row k inside a tile
+  // LDS destination of this wave's piece of (buffer buf, half-tile which = dY0, dY1, X0, X1).  The two buffers interleave at slot
+  // granularity so that the buffer offset fits the ds_read immediate (all transposed reads then need no address VALU).
+  __device__ __forceinline__ char* dst(int buf, int which) const { return smem + (which * 2 + buf) * HALF + wid * 1024; }
+};
+
+// Any geometry: each of the thread's two rows carries its pixel row, its output coordinates and the first input row of its image; the
+// source row of the tap is decoded from them per tile, then they advance by 64 pixels.
+struct StageGeneral : StageBase {
+  bool yok[2][2], xok[2][2];                         // [k][h]: channel half h of row k exists (OC / IC tail)
+  int my[2];                                         // pixel row of the NEXT Y tile
+  int xm[2], xoy[2], xox[2], xbase[2];               // NEXT X tile: pixel row, output coordinates, first input row of the image
+  const char* xrow[2];                               // source pixel row (chunk lc[k], half 0) of the X tile being issued, or nullptr
+  int M1;                                            // rows of the first segment
+
+  __device__ __forceinline__ StageGeneral(const Args& a_, const WgTile& t_, char* smem_, int tid_, int wid_) : StageBase(a_, t_, smem_, tid_, wid_) {
+    M1 = d.N * d.OH * d.OW;
 #pragma unroll
-    for (int k = 0; k < 2; ++k)
+    for (int k = 0; k < 2; ++k) {
+      my[k] = xm[k] = t.m_begin + row(k);
+      const wseg_rowgeo rg = wseg_decode_row(d, min(xm[k], a.M - 1));
+      xoy[k] = rg.oy; xox[k] = rg.ox; xbase[k] = (int)rg.in_base;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        rry[k][h] = yok[k][h] ? (tid >> 4) + 32 * k : 0x40000000;
-        rrx[k][h] = xok[k][h] ? (tid >> 4) + 32 * k : 0x40000000;
+        yok[k][h] = t.oc0 + 128 * h + lc[k] * 8 < d.OC;
+        xok[k][h] = t.ic0 + 128 * h + lc[k] * 8 < d.IC;
       }
-  }
-  auto x_prepare = [&]() {                           // call once per X tile, before its two half issues; advances to the next tile
-    if constexpr (UNIT) {
-      if (tx_idx == nA && nA > 0 && nB > 0) {        // (wave-uniform, once) enter the second segment: jump the pointers, decode afresh
-        const long jump = (long)(b_begin - x_m) * d.ld_x * 2 + xcross;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          xptr[k] += jump;
-          const wseg_rowgeo rg = wseg_decode_row(d, min(b_begin + (tid >> 4) + 32 * k, a.M - 1));
-          xoy[k] = rg.oy; xox[k] = rg.ox;
-        }
-        x_m = b_begin; x_lim = m_end; x_s2 = true;
-      }
-      const int OHs = x_s2 ? d.OH2 : d.OH, OWs = x_s2 ? d.OW2 : d.OW;
-      const int r64 = x_s2 ? a.r64_2 : a.r64_1, q64 = x_s2 ? a.q64_2 : a.q64_1;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        xin[k] = (unsigned)(xoy[k] + dy) < (unsigned)OHs && (unsigned)(xox[k] + dx) < (unsigned)OWs;
-        int ox = xox[k] + r64, oy = xoy[k] + q64;    // advance 64 rows (host guarantees one row wrap at most: simple_adv)
-        const bool cx = ox >= OWs;
-        ox = cx ? ox - OWs : ox; oy = cx ? oy + 1 : oy;
-        oy = oy >= OHs ? oy - OHs : oy;
-        xox[k] = ox; xoy[k] = oy;
-      }
-      return;
     }
+  }
+  __device__ __forceinline__ int ntiles() const { return (t.m_end - t.m_begin + PK - 1) / PK; }
+
+  __device__ __forceinline__ void prepare_x() {
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const bool s2 = d.OH2 != 0 && xm[k] >= M1;
       const int OHs = s2 ? d.OH2 : d.OH, OWs = s2 ? d.OW2 : d.OW, IHs = s2 ? d.IH2 : d.IH, IWs = s2 ? d.IW2 : d.IW;
       const int mn = xm[k] + PK;
       xrow[k] = nullptr;
-      if (xm[k] < m_end) {
-        const int iy = xoy[k] * d.stride + ky * d.dil - d.pad;
-        const int ix = xox[k] * d.stride + kx * d.dil - d.pad;
+      if (xm[k] < t.m_end) {
+        const int iy = xoy[k] * d.stride + t.ky * d.dil - d.pad;
+        const int ix = xox[k] * d.stride + t.kx * d.dil - d.pad;
         if (iy >= 0 && iy < IHs && ix >= 0 && ix < IWs)
-          xrow[k] = X + ((size_t)(xbase[k] + iy * IWs + ix) * d.ld_x + ic0 + lc[k] * 8) * 2;
+          xrow[k] = reinterpret_cast<const char*>(d.x) + ((size_t)(xbase[k] + iy * IWs + ix) * d.ld_x + t.ic0 + lc[k] * 8) * 2;
       }
       // advance 64 pixel rows
       if (d.OH2 != 0 && xm[k] < M1 && mn >= M1) {     // crosses into the second segment: decode afresh (rare)
@@ -477,76 +427,160 @@ __device__ __forceinline__ void conv_wgrad_pipe_tile(const Args& a, char* smem, 
       }
       xm[k] = mn;
     }
-  };
-  auto issue_x = [&](int h, int buf) {
-    char* dst = smem + slot_off(buf, 2 + h) + wid * 1024;
-    if constexpr (UNIT) {
-      const int rem = WG_DIAG(a) >= 4 ? 0 : x_lim - x_m;  // rows of this tile inside its sub-range (diag: X from the zero page)
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const char* p = (xin[k] && rrx[k][h] < rem) ? xptr[k] + h * 256 : zsrc;
-        glds16(p, dst + k * 8192);
-      }
-      if (h == 1) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k) xptr[k] += xstep;
-        x_m += PK; ++tx_idx;
-      }
-      return;
-    }
+  }
+  __device__ __forceinline__ void issue_x(int h, int buf) {
+    char* to = dst(buf, 2 + h);
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const char* p = (xrow[k] && xok[k][h]) ? xrow[k] + h * 256 : zsrc;
-      glds16(p, dst + k * 8192);
+      glds16(p, to + k * 8192);
     }
-  };
-  auto issue_y = [&](int h, int buf) {               // half h of the NEXT Y tile; h == 1 advances to the following tile
-    char* dst = smem + slot_off(buf, h) + wid * 1024;
-    if constexpr (UNIT) {
-      if (h == 0 && ty_idx == nA && nA > 0 && nB > 0) {   // (wave-uniform, once) enter the second segment
-        const long jump = (long)(b_begin - y_m) * d.ld_dy * 2;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) ybase[k] += jump;
-        y_m = b_begin; y_lim = m_end;
-      }
-      const int rem = WG_DIAG(a) == 5 ? 0 : y_lim - y_m;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const char* p = rry[k][h] < rem ? ybase[k] + h * 256 : zsrc;
-        glds16(p, dst + k * 8192);
-      }
-      if (h == 1) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k) ybase[k] += ystep;
-        y_m += PK; ++ty_idx;
-      }
-      return;
-    }
+  }
+  __device__ __forceinline__ void issue_y(int h, int buf) {
+    char* to = dst(buf, h);
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-      const char* p = (my[k] < m_end && yok[k][h] && WG_DIAG(a) != 5) ? ybase[k] + h * 256 : zsrc;
-      glds16(p, dst + k * 8192);
+      const char* p = (my[k] < t.m_end && yok[k][h] && WG_DIAG(a) != 5) ? ybase[k] + h * 256 : zsrc;
+      glds16(p, to + k * 8192);
     }
     if (h == 1) {
 #pragma unroll
       for (int k = 0; k < 2; ++k) { ybase[k] += ystep; my[k] += PK; }
     }
-  };
+  }
+};
+
+// UNIT geometry: stride 1 and IH == OH, IW == OW in both segments.  The input pixel of (output row m, tap) = m + dy*W + dx inside its
+// segment, so the X source is a running pointer (+64 rows per K-tile, + a constant when crossing into the second segment) and only the
+// VALIDITY needs (oy, ox).
+// The K-tiles never straddle the boundary between the two row segments (views): the pixel range is walked as [m_begin, min(m_end, M1))
+// then [max(m_begin, M1), m_end), each in 64-row tiles (at most one tile more than a straight walk; rows past a sub-range's end read the
+// zero page on both operands).  All geometry of a tile is then wave-uniform (scalars): per row there remain two bounds tests, the
+// (oy, ox) advance and the source select.
+struct StageUnit : StageBase {
+  int dy, dx;                                        // the tap's offset in input rows / columns
+  const char* xptr[2];                               // X source of the NEXT X tile (row k, chunk lc[k], half 0), valid or not
+  size_t xstep;                                      // 64 rows of X
+  long xcross;                                       // pointer correction when a row enters segment 2
+  int b_begin, nA, nB;                               // the second sub-range's first row; tiles of the two sub-ranges
+  int ty_idx = 0, tx_idx = 0;                        // index of the NEXT dY / X tile to issue
+  int y_m, x_m;                                      // its first pixel row
+  int y_lim, x_lim;                                  // end of its sub-range
+  bool x_s2;                                         // the X tile's segment
+  int xoy[2], xox[2];                                // output coordinates of row k of the NEXT X tile
+  int rry[2][2], rrx[2][2];                          // row inside the tile per (k, h); huge where the channel half does not exist
+  bool xin[2] = {false, false};                      // the X tile being issued: tap lands inside the image
+
+  __device__ __forceinline__ StageUnit(const Args& a_, const WgTile& t_, char* smem_, int tid_, int wid_) : StageBase(a_, t_, smem_, tid_, wid_) {
+    const int M1 = d.N * d.OH * d.OW;
+    dy = t.ky * d.dil - d.pad; dx = t.kx * d.dil - d.pad;
+    const bool s2 = d.OH2 != 0 && t.m_begin >= M1;   // the workgroup's FIRST segment (uniform); the switch adds xcross
+    const long shift = (long)dy * (s2 ? d.IW2 : d.IW) + dx;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const wseg_rowgeo rg = wseg_decode_row(d, min(t.m_begin + row(k), a.M - 1));
+      xoy[k] = rg.oy; xox[k] = rg.ox;
+      xptr[k] = reinterpret_cast<const char*>(d.x) + (((long)(t.m_begin + row(k)) + shift) * d.ld_x + t.ic0 + lc[k] * 8) * 2;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        rry[k][h] = t.oc0 + 128 * h + lc[k] * 8 < d.OC ? row(k) : 0x40000000;
+        rrx[k][h] = t.ic0 + 128 * h + lc[k] * 8 < d.IC ? row(k) : 0x40000000;
+      }
+    }
+    xstep = (size_t)PK * d.ld_x * 2;
+    xcross = (long)dy * (d.IW2 - d.IW) * d.ld_x * 2;
+    const int seg_end = d.OH2 != 0 ? M1 : a.M;
+    const int a_end = min(t.m_end, seg_end);
+    b_begin = max(t.m_begin, seg_end);
+    nA = t.m_begin < a_end ? (a_end - t.m_begin + PK - 1) / PK : 0;
+    nB = t.m_end > b_begin ? (t.m_end - b_begin + PK - 1) / PK : 0;
+    y_m = x_m = t.m_begin;
+    y_lim = x_lim = nA > 0 ? a_end : t.m_end;
+    x_s2 = nA == 0 && d.OH2 != 0;
+  }
+  __device__ __forceinline__ int ntiles() const { return nA + nB; }
+
+  __device__ __forceinline__ void prepare_x() {
+    if (tx_idx == nA && nA > 0 && nB > 0) {          // (wave-uniform, once) enter the second segment: jump the pointers, decode afresh
+      const long jump = (long)(b_begin - x_m) * d.ld_x * 2 + xcross;
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        xptr[k] += jump;
+        const wseg_rowgeo rg = wseg_decode_row(d, min(b_begin + row(k), a.M - 1));
+        xoy[k] = rg.oy; xox[k] = rg.ox;
+      }
+      x_m = b_begin; x_lim = t.m_end; x_s2 = true;
+    }
+    const int OHs = x_s2 ? d.OH2 : d.OH, OWs = x_s2 ? d.OW2 : d.OW;
+    const int r64 = x_s2 ? a.r64_2 : a.r64_1, q64 = x_s2 ? a.q64_2 : a.q64_1;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      xin[k] = (unsigned)(xoy[k] + dy) < (unsigned)OHs && (unsigned)(xox[k] + dx) < (unsigned)OWs;
+      int ox = xox[k] + r64, oy = xoy[k] + q64;      // advance 64 rows (host guarantees one row wrap at most: simple_adv)
+      const bool cx = ox >= OWs;
+      ox = cx ? ox - OWs : ox; oy = cx ? oy + 1 : oy;
+      oy = oy >= OHs ? oy - OHs : oy;
+      xox[k] = ox; xoy[k] = oy;
+    }
+  }
+  __device__ __forceinline__ void issue_x(int h, int buf) {
+    char* to = dst(buf, 2 + h);
+    const int rem = WG_DIAG(a) >= 4 ? 0 : x_lim - x_m;    // rows of this tile inside its sub-range (diag: X from the zero page)
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const char* p = (xin[k] && rrx[k][h] < rem) ? xptr[k] + h * 256 : zsrc;
+      glds16(p, to + k * 8192);
+    }
+    if (h == 1) {
+#pragma unroll
+      for (int k = 0; k < 2; ++k) xptr[k] += xstep;
+      x_m += PK; ++tx_idx;
+    }
+  }
+  __device__ __forceinline__ void issue_y(int h, int buf) {
+    if (h == 0 && ty_idx == nA && nA > 0 && nB > 0) {     // (wave-uniform, once) enter the second segment
+      const long jump = (long)(b_begin - y_m) * d.ld_dy * 2;
+#pragma unroll
+      for (int k = 0; k < 2; ++k) ybase[k] += jump;
+      y_m = b_begin; y_lim = t.m_end;
+    }
+    char* to = dst(buf, h);
+    const int rem = WG_DIAG(a) == 5 ? 0 : y_lim - y_m;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const char* p = rry[k][h] < rem ? ybase[k] + h * 256 : zsrc;
+      glds16(p, to + k * 8192);
+    }
+    if (h == 1) {
+#pragma unroll
+      for (int k = 0; k < 2; ++k) ybase[k] += ystep;
+      y_m += PK; ++ty_idx;
+    }
+  }
+};
+
+// ---- 256x256 bf16 phase-pipelined variant (the schedule validated in csrc/gemm256_probe.hip: 1.1-1.2 PF on
+// plain GEMM).  K-tile = 64 pixels; LDS = 2 K-tiles x 4 half-tile slots {dY ch 0-127, dY ch 128-255, X ch 0-127,
+// X ch 128-255}, each [64 pixels][128 ch] = 16 KiB.  A K-tile is two lock-step phases of 32 MFMAs per wave (see `ktile`);
+// the first refills dY0/dY1(u+1), the second X0/X1(u+2), slots every wave has finished reading, and the only DMA wait is
+// a counted s_waitcnt vmcnt(4) in the second.  One raw s_barrier per phase.  The transposed
+// fragment reads go through inline asm (hipcc would put vmcnt(0) in front of ds_read_tr builtins while
+// LDS-DMA is in flight), with an explicit lgkmcnt(0) + sched_barrier before the MFMAs.
+template <int UNIT>                // UNIT 1: stride 1 and IH==OH, IW==OW in both segments (StageUnit), else StageGeneral
+__device__ __forceinline__ void conv_wgrad_pipe_tile(const Args& a, char* smem, const int bid) {   // (smem: the workgroup's 128 KiB LDS buffer)
+  constexpr int BO = 256, BI = 256;
+  constexpr int HALF = 16384, ROWB = 256;
+  const wseg_wgrad_desc& d = a.d;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const WgTile wt = wg_tile_of<BO, BI>(a, bid);
+  if (wt.m_begin >= wt.m_end) return;
+  std::conditional_t<UNIT != 0, StageUnit, StageGeneral> st(a, wt, smem, tid, wid);
 
   const int wr = wid >> 2, wc = wid & 3;
   const int fcol = lane & 15, fk = lane >> 4;
   const int q = (lane & 15) >> 2, p = lane & 3;
-  // per-lane byte offsets of the transposed reads inside a half-tile: [ks][h] row, swizzled 32-B block per channel tile
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
-  unsigned rowoff[2][2], rsw[2][2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int row = ks * 32 + fk * 8 + h * 4 + q;
-      rowoff[ks][h] = row * ROWB + p * 8;
-      rsw[ks][h] = (row & 3) | (((row >> 3) & 1) << 2);
-    }
 
   f32x4 acc[8][4];
 #pragma unroll
@@ -554,11 +588,11 @@ __device__ __forceinline__ void conv_wgrad_pipe_tile(const Args& a, char* smem, 
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  const int nt = UNIT ? nA + nB : (m_end - m_begin + PK - 1) / PK;
+  const int nt = st.ntiles();
   // prologue: tile 0 entirely + the X halves of tile 1
-  issue_y(0, 0); issue_y(1, 0);
-  x_prepare(); issue_x(0, 0); issue_x(1, 0);
-  if (nt > 1) { x_prepare(); issue_x(0, 1); issue_x(1, 1); asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
+  st.issue_y(0, 0); st.issue_y(1, 0);
+  st.prepare_x(); st.issue_x(0, 0); st.issue_x(1, 0);
+  if (nt > 1) { st.prepare_x(); st.issue_x(0, 1); st.issue_x(1, 1); asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   asm volatile("s_barrier" ::: "memory");
 
@@ -591,7 +625,7 @@ __device__ __forceinline__ void conv_wgrad_pipe_tile(const Args& a, char* smem, 
     // (b*HALF) and the (ks, h) row offsets (ks*32 + h*4 rows) are compile-time immediates.  12 registers, no VALU per read.
     unsigned LTA[8], LTB[4];
     {
-      const unsigned s_ = (unsigned)q | (((unsigned)fk & 1u) << 2);
+      const unsigned s_ = swz32(fk * 8 + q);                      // the swizzle of the lane's row
       const unsigned rowterm = lds0 + (unsigned)(fk * 8 + q) * ROWB + (unsigned)p * 8;
 #pragma unroll
       for (int t = 0; t < 8; ++t) LTA[t] = rowterm + (((unsigned)t ^ s_) << 5) + (unsigned)(wr * 2) * HALF;
@@ -614,7 +648,7 @@ __device__ __forceinline__ void conv_wgrad_pipe_tile(const Args& a, char* smem, 
         tr_read<BO + 0>(vb1[0][0][j], LTB[2 + j]); tr_read<BO + 1024>(vb1[0][1][j], LTB[2 + j]);
         tr_read<BO + 8192>(vb1[1][0][j], LTB[2 + j]); tr_read<BO + 9216>(vb1[1][1][j], LTB[2 + j]);
       }
-      if (u + 1 < nt && WG_DIAG(a) != 6) { issue_y(0, b ^ 1); issue_y(1, b ^ 1); }   // (diag 6, probe builds: no LDS-DMA request inside the loop — timing only)
+      if (u + 1 < nt && WG_DIAG(a) != 6) { st.issue_y(0, b ^ 1); st.issue_y(1, b ^ 1); }   // (diag 6, probe builds: no LDS-DMA request inside the loop — timing only)
       WAIT_LDS();
       PACK_A() PACK_B(b0, vb0) PACK_B(b1, vb1)
       MFMA_Q(0, 0, b0);
@@ -626,7 +660,7 @@ __device__ __forceinline__ void conv_wgrad_pipe_tile(const Args& a, char* smem, 
         tr_read<BO + 0>(va[0][0][i], LTA[4 + i]); tr_read<BO + 1024>(va[0][1][i], LTA[4 + i]);
         tr_read<BO + 8192>(va[1][0][i], LTA[4 + i]); tr_read<BO + 9216>(va[1][1][i], LTA[4 + i]);
       }
-      if (u + 2 < nt) { if (WG_DIAG(a) != 6) { x_prepare(); issue_x(0, b); issue_x(1, b); } asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
+      if (u + 2 < nt) { if (WG_DIAG(a) != 6) { st.prepare_x(); st.issue_x(0, b); st.issue_x(1, b); } asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       WAIT_LDS();
       PACK_A()
@@ -647,60 +681,27 @@ __device__ __forceinline__ void conv_wgrad_pipe_tile(const Args& a, char* smem, 
 #undef MFMA_Q
   __syncthreads();                                 // every wave is done with the pipeline buffers
 
-  if (a.wave_epi) {
-    // Epilogue, wave-local (what every launch runs; wave_epi = 0 = the block-wide image below): every wave adds its own 128(oc) x 64(ic) accumulator tile to dW through
-    // a private 16-row LDS scratch, no workgroup barrier; one atomic wave-instruction = 64 consecutive floats (256 B).
-    constexpr int WLD = 64 + 4;
-    float* wimg = reinterpret_cast<float*>(smem) + wid * (16 * WLD);
-    const size_t row_stride = (size_t)a.taps * d.IC_dw;
-    const int ic = ic0 + wc * 64 + lane;
-    const bool ic_ok = ic < d.IC_dw;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) wimg[(fk * 4 + e) * WLD + j * 16 + fcol] = acc[i][j][e];
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      const int oc_base = oc0 + wr * 128 + i * 16;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int oc = oc_base + r;
-        if (ic_ok && oc < d.OC_dw) atomicAdd(&d.dw[(size_t)oc * row_stride + (size_t)tap * d.IC_dw + ic], wimg[r * WLD + lane]);
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-    return;
-  }
-  float* img = reinterpret_cast<float*>(smem);
+  // Epilogue, wave-local: every wave adds its own 128(oc) x 64(ic) accumulator tile to dW through a private 16-row LDS scratch,
+  // no workgroup barrier; one atomic wave-instruction = 64 consecutive floats (256 B).
+  constexpr int WLD = 64 + 4;
+  float* wimg = reinterpret_cast<float*>(smem) + wid * (16 * WLD);
   const size_t row_stride = (size_t)a.taps * d.IC_dw;
-#pragma unroll 1
-  for (int ps = 0; ps < BO / EPI_ROWS; ++ps) {
+  const int ic = wt.ic0 + wc * 64 + lane;
+  const bool ic_ok = ic < d.IC_dw;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int t = wr * 8 + i;
-      if (t / 4 == ps) {
-        const int row = (t % 4) * 16 + fk * 4;
+  for (int i = 0; i < 8; ++i) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int col = (wc * 4 + j) * 16 + fcol;
+    for (int j = 0; j < 4; ++j)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) img[(row + e) * EPI_LD + col] = acc[i][j][e];
-        }
-      }
+      for (int e = 0; e < 4; ++e) wimg[(fk * 4 + e) * WLD + j * 16 + fcol] = acc[i][j][e];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const int oc_base = wt.oc0 + wr * 128 + i * 16;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int oc = oc_base + r;
+      if (ic_ok && oc < d.OC_dw) atomicAdd(&d.dw[(size_t)oc * row_stride + (size_t)wt.tap * d.IC_dw + ic], wimg[r * WLD + lane]);
     }
-    __syncthreads();
-#pragma unroll 1
-    for (int idx = tid; idx < EPI_ROWS * BI; idx += NT) {
-      const int row = idx / BI, col = idx - row * BI;
-      const int oc = oc0 + ps * EPI_ROWS + row, ic = ic0 + col;
-      if (oc < d.OC_dw && ic < d.IC_dw) {
-        float* dst = &d.dw[(size_t)oc * row_stride + (size_t)tap * d.IC_dw + ic];
-        if (WG_DIAG(a) == 0) atomicAdd(dst, img[row * EPI_LD + col]);
-        else if (WG_DIAG(a) == 2) *dst = img[row * EPI_LD + col];       // (timing diagnostics only: plain store / nothing)
-      }
-    }
-    __syncthreads();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
 }
 
@@ -769,7 +770,6 @@ static int wgrad_plan(const wseg_wgrad_desc* d, Plan& pl) {
 #else
   a.diag = 0;
 #endif
-  a.wave_epi = 1;
   pl.unit = a.simple_adv && d->stride == 1 && d->IH == d->OH && d->IW == d->OW && (d->OH2 == 0 || (d->IH2 == d->OH2 && d->IW2 == d->OW2));
   pl.pipe = big;
   WSEG_CHECK(d->dw_rot == 0 || !pl.pipe, "conv_wgrad: dw_rot is supported by the 128-tile kernel only");
