@@ -185,6 +185,135 @@ def test_conv_epilogues(dt, OC, bm):
     assert float(wide[..., :64].abs().max()) == 0 and float(wide[..., 64 + OC:].abs().max()) == 0
 
 
+# ---- test_conv_epilogue_operands: every operand combination of the fused epilogue the network launches, one or two launches per case, against
+# torch on the CPU in float64 from inputs already rounded to the storage dtype.  300 rows (N = 2, 15 x 10): one full + one partial tile at 256,
+# 224 and 128 rows.  (family: storage dtype, bm_hint; bm_hint 0 = the planner's own choice, the 64 / 128-row tiles at these sizes.)
+EPI_TOL = {"f32": dict(rtol=2e-5, atol=2e-5), "x3": dict(rtol=1e-4, atol=1e-4), "bf16": dict(rtol=2e-2, atol=3e-2)}
+EPI_FAMILIES = [("f32", 0), ("bf16", 0), ("x3", 0), ("f32", 128), ("bf16", 128), ("bf16", 256), ("x3", 256), ("bf16", 224), ("bf16", 259)]
+EPI_SETS = ["post_out_out2", "pre_out2_only", "relu_lt_tail", "epi1_mask_post", "epi1_mask_drop"]
+EPI_CASES = ([(dt, bm, s) for dt, bm in EPI_FAMILIES for s in EPI_SETS] +
+             [(dt, bm, "elu") for dt in ("f32", "bf16") for bm in (64, 128)] +       # (the planner sends epi 3 nowhere else)
+             [("bf16", 256, "perm_mask_post")])
+_epi_cache = {}
+
+
+def _epi_problem(dt, OC):
+    """Seeded operands of the 300-row 64 -> OC 3x3 convolution, rounded to the storage dtype, and the float64 convolution of them (computed once
+    per (dtype, OC), shared by the cases, never written to)."""
+    key = (dt, OC)
+    if key not in _epi_cache:
+        tdt = torch.bfloat16 if dt == "bf16" else torch.float32
+        N, H, W, IC, k = 2, 15, 10, 64, 3
+        p = dict(N=N, H=H, W=W, IC=IC, k=k, OC=OC, tdt=tdt)
+        p["x"] = _rand((N, IC, H, W), 1).to(tdt)
+        p["w"] = _rand((OC, IC, k, k), 2, 0.06).to(tdt)
+        for name, seed in (("post", 4), ("pre", 5), ("mask", 9)):
+            p[name] = _rand((N, OC, H, W), seed).to(tdt)
+        p["scale"], p["shift"] = _rand((OC,), 6) + 1.5, _rand((OC,), 7)
+        p["drop"] = (torch.rand(N, OC, generator=torch.Generator().manual_seed(8)) > 0.5).float() * 2
+        p["y"] = F.conv2d(p["x"].double(), p["w"].double(), None, 1, 1, 1)
+        _epi_cache[key] = p
+    return _epi_cache[key]
+
+
+def _epi_weights(p, dt, rows):
+    """[rows][k*k][IC] forward pack on the GPU (rows >= OC: zero-padded, wseg_conv_desc.w_rows), pre-split for the split-bf16 kernels"""
+    from wseg_amd import _lib as L
+    OC, IC, k = p["OC"], p["IC"], p["k"]
+    wf = torch.zeros(rows, k * k, IC, device="cuda", dtype=p["tdt"])
+    wf[:OC] = p["w"].permute(0, 2, 3, 1).reshape(OC, k * k, IC).to("cuda")
+    if dt == "x3":
+        w32, wf = wf, torch.empty_like(wf)
+        L.pack_x3(w32, wf)
+    return wf
+
+
+@pytest.mark.parametrize("dt,bm,opset", EPI_CASES)
+def test_conv_epilogue_operands(dt, bm, opset):
+    """The fused epilogue with the operand sets the network uses, on every kernel family that takes them: a single residual (r_post alone: the
+    prefetched slot of the wave-local epilogue; r_pre alone), out2 without out, relu_out2 = 0, relu_lt with a channel tail behind it (the head
+    launch: relu_lt = 128, and w_rows = 256 on the 256-column tiles), the masked scale with and without residual / dropout, ELU, and the masked
+    scale of a stride-2 data gradient whose rows run in parity-class order (operands addressed through the true row)."""
+    from wseg_amd import _lib as L
+    dev = "cuda"
+    tol = EPI_TOL[dt]
+    cdt = L.F32X3 if dt == "x3" else None
+    fam = CONV_FAMILY[bm] if bm else ROWS_64_128
+    g = lambda t: _nhwc(t).to(dev)
+    bc = lambda v: v.double().view(1, -1, 1, 1)
+    check = lambda got, ref: np.testing.assert_allclose(got.double().cpu().numpy(), _nhwc(ref).numpy(), **tol)
+
+    if opset == "perm_mask_post":
+        # stride-2 3x3 data gradient 256 -> 256 onto a 12 x 12 map: 288 rows = 4 parity classes of 72; tile 0 mixes classes, tile 1 lies inside one
+        N, H, W, C, k = 2, 12, 12, 256, 3
+        tdt = torch.bfloat16
+        x = _rand((N, C, H, W), 1).to(tdt).double().requires_grad_(True)
+        w = _rand((C, C, k, k), 2, (2.0 / (C * k * k)) ** 0.5).to(tdt)
+        dy = _rand((N, C, H // 2, W // 2), 3).to(tdt)
+        post, mask = _rand((N, C, H, W), 4).to(tdt), _rand((N, C, H, W), 9).to(tdt)
+        F.conv2d(x, w.double(), None, 2, 1, 1).backward(dy.double())
+        ref = x.grad * (mask > 0).double() + post.double()
+        wt = torch.empty(C, k * k, C, device=dev, dtype=tdt)
+        L.pack_weights(w.float().permute(0, 2, 3, 1).contiguous().to(dev), None, wt, C, k * k, C, C, C, L.dtype_code(wt))
+        dx = torch.full((N, H, W, C), float("nan"), device=dev, dtype=tdt)
+        _conv(fam, g(dy), wt, dx, N=N, IH=H // 2, IW=W // 2, IC=C, OH=H, OW=W, OC=C, KH=k, KW=k, stride=2, pad=1, mode=1, epi=1,
+              mask=g(mask), r_post=g(post), bm_hint=bm, perm=1)
+        check(dx, ref)
+        return
+
+    big = bm in (224, 256)
+    if opset == "relu_lt_tail":
+        OC = 256 if bm == 259 else 152          # 152: 24 live columns in the second 128-column tile / a 256-column tile masked behind column 152
+    else:
+        OC = 256 if big else 128
+    p = _epi_problem(dt, OC)
+    N, H, W, IC, k, tdt, y = p["N"], p["H"], p["W"], p["IC"], p["k"], p["tdt"], p["y"]
+    w_rows = 256 if (big and OC % 256) else 0
+    wf = _epi_weights(p, dt, max(OC, w_rows))
+    xg = g(p["x"])
+    geo = dict(N=N, IH=H, IW=W, IC=IC, OH=H, OW=W, OC=OC, KH=k, KW=k, pad=1, bm_hint=bm, dtype=cdt)
+    new = lambda: torch.full((N, H, W, OC), float("nan"), device=dev, dtype=tdt)
+    scale, shift, drop = p["scale"].to(dev), p["shift"].to(dev), p["drop"].to(dev)
+    dropb = p["drop"].double().view(N, OC, 1, 1)
+
+    if opset == "post_out_out2":
+        out, out2 = new(), new()
+        _conv(fam, xg, wf, out, out2, r_post=g(p["post"]), scale=scale, shift=shift, drop=drop, relu_out2=1, **geo)
+        raw = y + p["post"].double()
+        check(out, raw)
+        check(out2, F.relu(raw * bc(p["scale"]) + bc(p["shift"])) * dropb)
+    elif opset == "pre_out2_only":
+        out2 = new()
+        _conv(fam, xg, wf, None, out2, r_pre=g(p["pre"]), scale=scale, shift=shift, relu_out2=0, **geo)
+        ref = (y + p["pre"].double()) * bc(p["scale"]) + bc(p["shift"])
+        assert float(ref.min()) < -0.5                      # (a ReLU here would show)
+        check(out2, ref)
+    elif opset == "relu_lt_tail":
+        RL, LD, OFF, GUARD = 128, OC + 128, 64, -7.0
+        wide = torch.full((N, H, W, LD), GUARD, device=dev, dtype=tdt)
+        _conv(fam, xg, wf, wide[..., OFF:], relu_lt=RL, ld_out=LD, w_rows=w_rows, **geo)
+        ref = torch.cat([F.relu(y[:, :RL]), y[:, RL:]], dim=1)
+        got = wide[..., OFF:OFF + OC]
+        check(got, ref)
+        assert bool((wide[..., :OFF] == GUARD).all()) and bool((wide[..., OFF + OC:] == GUARD).all())
+        neg = _nhwc(y[:, RL:]) < -0.05                      # columns >= relu_lt keep their negative values, columns below it have none
+        assert bool(neg.any()) and bool((got[..., RL:].double().cpu()[neg] < 0).all())
+        assert bool((got[..., :RL] >= 0).all())
+    elif opset == "epi1_mask_post":
+        out = new()
+        _conv(fam, xg, wf, out, epi=1, scale=scale, mask=g(p["mask"]), r_post=g(p["post"]), **geo)
+        check(out, y * bc(p["scale"]) * (p["mask"] > 0).double() + p["post"].double())
+    elif opset == "epi1_mask_drop":
+        out = new()
+        _conv(fam, xg, wf, out, epi=1, scale=scale, mask=g(p["mask"]), drop=drop, **geo)
+        check(out, y * bc(p["scale"]) * dropb * (p["mask"] > 0).double())
+    else:
+        assert opset == "elu"
+        out = new()
+        _conv(fam, xg, wf, out, epi=3, **geo)
+        check(out, F.elu(y))
+
+
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
 def test_stem(dt):
     from wseg_amd import _lib as L

@@ -17,7 +17,9 @@ mkdir -p $OBJ
 pids=()
 for f in $SRCS; do
   o=$OBJ/${f%.hip}.o
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ conv_wgrad_kernels.h -nt "$o" ] || [ "$(cat $OBJ/.flags 2>/dev/null)" != "$FLAGS" ] || [ common.h -nt "$o" ] || [ ../../include/wseg_hip.h -nt "$o" ]; then
+  stale=0                                    # an object is rebuilt when its source, ANY header of this directory or the C ABI header is newer
+  for h in "$f" *.h ../../include/wseg_hip.h; do if [ "$h" -nt "$o" ]; then stale=1; fi; done
+  if [ ! -f "$o" ] || [ $stale = 1 ] || [ "$(cat $OBJ/.flags 2>/dev/null)" != "$FLAGS" ]; then
     hipcc $FLAGS -c "$f" -o "$o" &
     pids+=($!)
   fi

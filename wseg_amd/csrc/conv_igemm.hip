@@ -2,79 +2,23 @@
 //
 //   C[m][oc] = sum_{tap} sum_{ic} IN[pix(m,tap)][ic] * W[oc][tap][ic]
 //
-// Both operands are K-contiguous ("pixel rows" of channels, weight rows of [tap][ic]), so both
-// LDS tiles are [128 rows][128 B] and are filled by LDS-DMA (global_load_lds_dwordx4): the
-// im2col gather is nothing but the per-lane SOURCE address; zero padding is a 256-B zero page.
-// Tile 128(M pixels) x 128(N out-channels) x 128 B of K per step, 4 waves (2x2), each wave a
-// 64x64 sub-tile = 4x4 MFMA 16x16 accumulators.  bf16: v_mfma_f32_16x16x32_bf16;
-// f32 (parity mode): v_mfma_f32_16x16x4_f32 (bit-exact f32 fma chain).
-// LDS rows are XOR-swizzled at 16-B granularity (phys = chunk ^ ((row>>1)&7)) — applied on the
-// DMA source side and on the ds_read side (the LDS image itself stays lane-linear).
+// Both operands are K-contiguous ("pixel rows" of channels, weight rows of [tap][ic]), so every LDS tile is [rows][128 B] and is
+// filled by LDS-DMA (global_load_lds_dwordx4): the im2col gather is nothing but the per-lane SOURCE address; zero padding is a
+// 256-B zero page.  LDS rows are XOR-swizzled at 16-B granularity (phys = chunk ^ ((row>>1)&7)) — applied on the DMA source side
+// and on the ds_read side (the LDS image itself stays lane-linear).  Three kernel families and one joint grid, chosen by conv_plan:
+//   conv_igemm_kernel<DT, EPI, BM>            64 / 128 rows x 128 columns, 4 waves (2x2), double-buffered, block-wide LDS-image epilogue.
+//                                             f32 (v_mfma_f32_16x16x4_f32, bit-exact fma chain), bf16, split-bf16; every epilogue.
+//   conv_igemm256_kernel<EPI, NI, DT, TAPF>   256 / 224 rows x 256 columns, 8 waves (2x4), 2-phase ping-pong, wave-local epilogue
+//                                             (conv_igemm256_tile); bf16 / split-bf16.  TAPF: 32-bit tap arithmetic; else the full decode.
+//   conv_igemm512x128_kernel<EPI>             512 rows x 128 columns, 8 waves (4x2), same schedule and epilogue; bf16, OC % 128 == 0.
+//   conv_bwd_pair_kernel<EPI, NI, UNIT>       a data gradient (conv_igemm256_tile) and a weight gradient (conv_wgrad_kernels.h) in one grid.
+// The fused-epilogue arithmetic (EPI 0..3) is written in epilogue_image and again in wave_local_epilogue_batch: a change to one must be made
+// in the other (tests/test_gpu_conv.py, test_conv_epilogue_operands, runs every operand set of the network through both).
 #include <stdlib.h>
 #include <algorithm>
 #include "common.h"
 #include "conv_wgrad_kernels.h"   // (wseg_wg::…: the weight-gradient tile body and its host-side plan, for wseg_conv_bwd_pair)
-
-#ifdef WSEG_PROBES
-// In-kernel stamps of the 256-tile body (probe builds only: `WSEG_PROBES=1 bash build.sh`): per workgroup 8 x s_memrealtime (100 MHz) — entry, gather
-// set-up done, first tiles landed, main loop done (early wave group), tile done; slots 5 / 6: main loop / tile done of the late group (wave 4);
-// slot 7: XCC id.  Written to a buffer of their own that no kernel reads (scripts/conv_tile_breakdown.py fetches it).
-__device__ unsigned long long g_wseg_stamps[24 * 4096];   // per workgroup: 8 wall-clock stamps, then (WSEG_SLOTS builds) 8 slot sums of wave 0 and 8 of wave 4
-#define WSEG_STAMP(slot, wave)                                                                                  \
-  do { if (threadIdx.x == (wave) * 64 && bid < 4096) g_wseg_stamps[bid * 24 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-extern "C" int wseg_debug_stamps(void* out, size_t bytes) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wseg_stamps), bytes < sizeof(g_wseg_stamps) ? bytes : sizeof(g_wseg_stamps)) == hipSuccess ? 0 : -1;
-}
-#define WSEG_CSTAMP(slot, wave)   /* shader-clock stamp (s_memtime): with the wall-clock stamps beside it, the clock the loop ran at */ \
-  do { if (threadIdx.x == (wave) * 64 && bid < 4096) g_wseg_stamps[bid * 24 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
-// probe-only timing switches (results wrong by design): bit 0 = request the A tile only on every 9th K-tile, bit 1 = no B requests after the prologue,
-// bit 2 = no A requests after the prologue, bit 3 = the A pointers never move (every request re-reads the tile's first K-tile: cache-resident), bit 4 = the same for B, bit 5 = the wave-local epilogue stores nothing (its loads and LDS round trips stay), bit 6 = it loads nothing either
-__device__ int g_wseg_diag;
-extern "C" int wseg_debug_set_diag(int v) { return hipMemcpyToSymbol(HIP_SYMBOL(g_wseg_diag), &v, sizeof(int)) == hipSuccess ? 0 : -1; }
-#define WSEG_DIAG_LOAD() const int diag_ = __builtin_amdgcn_readfirstlane(g_wseg_diag)
-#define WSEG_DIAG_A_OK(u) (!(diag_ & 4) && (!(diag_ & 1) || (u) % 9 == 8))
-#define WSEG_DIAG_B_OK() (!(diag_ & 2))
-#define WSEG_DIAG_A_MOVES() (!(diag_ & 8))
-#define WSEG_DIAG_B_MOVES() (!(diag_ & 16))
-#define WSEG_DIAG_EPI_STORES() (!(__builtin_amdgcn_readfirstlane(g_wseg_diag) & 32))
-#define WSEG_DIAG_EPI_LOADS() (!(__builtin_amdgcn_readfirstlane(g_wseg_diag) & 64))
-#else
-#define WSEG_STAMP(slot, wave) do { } while (0)
-#define WSEG_CSTAMP(slot, wave) do { } while (0)
-#define WSEG_DIAG_LOAD() do { } while (0)
-#define WSEG_DIAG_A_OK(u) true
-#define WSEG_DIAG_B_OK() true
-#define WSEG_DIAG_A_MOVES() true
-#define WSEG_DIAG_B_MOVES() true
-#define WSEG_DIAG_EPI_STORES() true
-#define WSEG_DIAG_EPI_LOADS() true
-#endif
-// WSEG_SLOTS (with WSEG_PROBES): cycles (s_memtime) a wave spends in each slot of the main loop, summed over the K-tiles: read slot 1 (fragment reads
-// until they have landed + LDS-DMA issue), barrier, MFMA slot 1, barrier, read slot 2 (+ the counted DMA wait), barrier, MFMA slot 2, barrier.
-// The stamps serialise what the real kernel overlaps (each waits for lgkmcnt(0)): read the SHARES, not the run time of this build.
-#if defined(WSEG_PROBES) && defined(WSEG_SLOTS)
-#define WSEG_SLOT_DECL() unsigned long long sl_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tp_ = 0
-#define WSEG_SLOT_BEGIN() asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tp_) :: "memory")
-#define WSEG_SLOT(i)                                                                                            \
-  do {                                                                                                          \
-    unsigned long long t_;                                                                                      \
-    __builtin_amdgcn_sched_barrier(0);                                                                          \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory");                               \
-    __builtin_amdgcn_sched_barrier(0);                                                                          \
-    sl_[i] += t_ - tp_; tp_ = t_;                                                                               \
-  } while (0)
-#define WSEG_SLOT_FLUSH()                                                                                       \
-  do {                                                                                                          \
-    if ((threadIdx.x == 0 || threadIdx.x == 256) && bid < 4096) {                                               \
-      _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) g_wseg_stamps[bid * 24 + 8 + (threadIdx.x >> 8) * 8 + i_] = sl_[i_]; \
-    }                                                                                                           \
-  } while (0)
-#else
-#define WSEG_SLOT_DECL() do { } while (0)
-#define WSEG_SLOT_BEGIN() do { } while (0)
-#define WSEG_SLOT(i) do { } while (0)
-#define WSEG_SLOT_FLUSH() do { } while (0)
-#endif
+#include "conv_probes.h"          // (WSEG_STAMP / WSEG_DIAG_* / WSEG_SLOT*: empty unless WSEG_PROBES)
 
 namespace {
 
@@ -120,7 +64,6 @@ __device__ __forceinline__ PermRow perm_decode(const Args& a, int m) {
   return r;
 }
 
-
 // ELU with alpha = 1 (F.elu; the AffinityNet head, network/resnet38_aff.py:44-47)
 __device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : expm1f(x); }
 
@@ -134,18 +77,18 @@ __device__ __forceinline__ void epilogue_coeffs(const wseg_conv_desc& d, int n0,
   if (d.shift != nullptr) load8<WSEG_F32>(d.shift, oc, sh);
 }
 
-// Fused epilogue over an f32 LDS image of ROWS x COLS accumulators (row stride LD floats), NT threads.
+// Block-wide fused epilogue of conv_igemm_kernel over its f32 LDS image of ROWS x BN accumulators (row stride EPI_LD floats), 256 threads.
 // Every thread owns ONE 8-channel column group.  All global operands of a chunk of rows are loaded before
 // any of them is consumed: one memory round trip per chunk instead of one per row (the dependent-load
 // chain was the whole cost of short-K layers).  Rows beyond M are clamped to row 0 for the loads and
 // predicated off at the stores (no divergent control flow).
-template <int DT, int EPI, int ROWS, int COLS, int LD, int NT, int MAXCHK = 4>
+template <int DT, int EPI, int ROWS>
 __device__ __forceinline__ void epilogue_image(const wseg_conv_desc& d, int M, const float* img, int m0, int n0, int tid,
                                                const float (&sc)[8], const float (&sh)[8]) {
-  constexpr int GPR = COLS / 8;                    // column groups per row
+  constexpr int NT = 256, GPR = BN / 8;            // threads; column groups per row
   constexpr int RPS = NT / GPR;                    // rows per sweep of the workgroup
   constexpr int SWEEPS = ROWS / RPS;
-  constexpr int CHK = SWEEPS < MAXCHK ? SWEEPS : MAXCHK;
+  constexpr int CHK = SWEEPS < 4 ? SWEEPS : 4;     // rows per thread whose operands are in flight together
   static_assert(NT % GPR == 0 && ROWS % RPS == 0 && SWEEPS % CHK == 0, "epilogue geometry");
   const int cv = (tid % GPR) * 8;
   const int oc_raw = n0 + cv;
@@ -185,12 +128,10 @@ __device__ __forceinline__ void epilogue_image(const wseg_conv_desc& d, int M, c
       const int row = ((c0 + j) * NT + tid) / GPR;
       const size_t m = mrow[j];
       float v[8];
-      {
-        const f32x4 p0 = *reinterpret_cast<const f32x4*>(&img[row * LD + cv]);
-        const f32x4 p1 = *reinterpret_cast<const f32x4*>(&img[row * LD + cv + 4]);
+      const f32x4 p0 = *reinterpret_cast<const f32x4*>(&img[row * EPI_LD + cv]);
+      const f32x4 p1 = *reinterpret_cast<const f32x4*>(&img[row * EPI_LD + cv + 4]);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { v[e] = p0[e]; v[4 + e] = p1[e]; }
-      }
+      for (int e = 0; e < 4; ++e) { v[e] = p0[e]; v[4 + e] = p1[e]; }
       if (has_pre) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += rpre[j][e];
@@ -606,20 +547,22 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const Args a) {
 
   float sc[8], sh[8];
   epilogue_coeffs(d, n0, (tid & 15) * 8, sc, sh);
-  epilogue_image<DT, EPI, BM, BN, EPI_LD, 256>(d, a.M, img, m0, n0, tid, sc, sh);
+  epilogue_image<DT, EPI, BM>(d, a.M, img, m0, n0, tid, sc, sh);
 }
 
-// ---- 256 x 256 bf16 phase-pipelined variant (large layers) ------------------------------------------------
+// ---- 256 x 256 phase-pipelined variant (large layers) -----------------------------------------------------
 // The 128^2 kernel above fills a CU at the L2->LDS rate with 64 FLOP per filled byte (a ~1.1 PF ceiling); a
-// 256x256 tile doubles that.  Schedule (validated on plain GEMM in csrc/gemm256_probe.hip, in production for
-// wgrad): 8 waves as 2(M) x 4(N), wave tile 128 x 64 = 8 x 4 accumulators; LDS = 2 K-tiles x 4 half-tile slots
-// {A0, A1, B0, B1}, each [128 rows][128 B] = 16 KiB.  A K-tile (one 128-B slice of one tap) is 4 phases of 16
-// MFMAs (one 64 x 32 quadrant of the wave tile); every phase refills ONE slot that all waves have finished
-// reading:    p1(u): A0(u+1)   p2(u): A1(u+1)   p3(u): B0(u+2)   p4(u): B1(u+2)
-// so LDS-DMA runs 1.5 tiles ahead with two tile buffers; the only DMA wait is ONE counted s_waitcnt vmcnt(4)
-// per K-tile (B0/B1(u+2) stay in flight) and one raw s_barrier per phase.  The im2col gather is again only the
-// per-lane source address (4 pixel rows per thread, re-derived once per tap); padded taps read the zero page.
-// Epilogue: 4 passes of 64 rows through a 65-KiB f32 LDS image, same fused epilogue as the 128^2 kernel.
+// 256x256 tile doubles that.  8 waves as 2(M) x 4(N), wave tile 128 x 64 = 8 x 4 accumulators; LDS = 2 K-tiles x
+// 4 half-tile slots {A0, A1, B0, B1}, each [128 rows][128 B] = 16 KiB.  A K-tile (one 128-B slice of one tap) is
+// TWO phases of 32 MFMAs (rows 0-63, then 64-127 of the wave tile), each a read slot (fragment ds_reads, LDS-DMA
+// requests, address work) and an MFMA slot with a raw s_barrier after each: two read slots and two MFMA slots per
+// K-tile.  PING-PONG: the two waves of a SIMD (w and w + 4, the two M halves) run one slot apart, so one reads
+// while the other feeds the matrix pipe.  Read slot 1 requests A(u+1), read slot 2 B(u+2); the only DMA wait is
+// ONE counted s_waitcnt vmcnt(4) per K-tile.  The im2col gather is again only the per-lane source address (4 pixel
+// rows per thread, re-derived once per tap); padded taps read the zero page.  Epilogue: wave-local (every wave
+// turns its own accumulators into 8-channel vectors through a private LDS scratch, no workgroup barrier; see
+// wave_local_epilogue_batch).  What stood here before — 4 phases of 16 MFMAs, lock-step forms, a block-wide
+// 65-KiB f32 LDS image — and why it lost: profiles/HISTORY.md.
 constexpr int HALF256 = 16384, TILE256 = 4 * HALF256;
 
 //
@@ -941,10 +884,6 @@ __global__ __launch_bounds__(512, 2) void conv_igemm256_kernel(const Args a) {
   conv_igemm256_tile<EPI, NI, DT, TAPF>(a, smem, blockIdx.x);
 }
 
-
-
-
-
 // ---- 512(M) x 128(N) bf16 phase-pipelined variant for OC = 128 layers (the frozen 224x224 prefix) -----------------------
 // Every kernel with a 128-wide column tile so far gave those layers ~680 TF/s whatever its pipeline depth, operand source
 // or address work; what they share is 32 MFMAs per wave per K-tile — half of the 256^2 kernel's — against the same fixed
@@ -1065,7 +1004,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm512x128_kernel(const Args a)
     __builtin_amdgcn_s_setprio(0);                                                                           \
   } while (0)
 
-  // 2-phase ping-pong (see conv_igemm256_kernel): waves 4-7 (wr >= 2) run one slot behind waves 0-3
+  // 2-phase ping-pong (see conv_igemm256_tile): waves 4-7 (wr >= 2) run one slot behind waves 0-3
   const int grp = wr >> 1;
   if (grp == 1) __builtin_amdgcn_s_barrier();
   for (int u = 0; u < nt; ++u) {
