@@ -243,9 +243,9 @@ int wseg_pcm_backward_bf16(const void* Fb, const void* Gb, const void* Gl, const
  *  pseudo_label       Q6 normalisation, bg threshold, argmax softmax(.*label) (:186-197)
  *  proto_candidates / proto_merge   per-class top-K (K = npix/8) over the batch, weighted mean, L2 norm (:199-209);
  *                     candidates are what ranks all-gather for global-batch prototypes
- *  nce_sims           L2-normalised features and their similarities to both prototype sets (:245-246, :262, :289)
  *  intra_weights      hard-pixel sampling: random half + similarity rank band per class (:302-331)
- *  nce_loss_grad      cross-prototype, cross-pseudo-label and intra-view InfoNCE + gradient w.r.t. the features (:261-334)
+ * plane_stats is implemented in csrc/maps.hip beside up_plane_stats, the pixel-to-prototype contrast (intra_weights*, nce_*) in csrc/nce.hip,
+ * everything else of this section in csrc/loss.hip.
  */
 size_t wseg_plane_stats_workspace_bytes(long planes);
 int wseg_plane_stats(const float* U, float* stats, long planes, int npix, void* workspace, void* stream);
@@ -283,22 +283,17 @@ int wseg_pseudo_label(const float* R, const float* label20, float bg_thr, int* y
 int wseg_proto_candidates(const float* ncam, const float* F, const int* tie_idx, float* cand_val, float* cand_feat, int* cand_const, int N, int npix, int K, void* stream);
 int wseg_proto_merge(const float* cand_val, const float* cand_feat, const int* cand_const, float* protos, int world, int K,
                      long rank_stride /* 0: contiguous [world][...] arrays; else elements between consecutive ranks' blocks (one gathered buffer) */, void* stream);
-int wseg_nce_sims(const float* F, const float* p_own, const float* p_oth, float* fn, float* nrm, float* S_own, float* S_oth, int P, void* stream);
 /* S_own: ld_s == 21: the [P,21] similarity table (the own-class entry is S_own[p*21 + y[p]]); ld_s == 1: one own-class similarity per pixel
  * (row 1 of the records below) */
 int wseg_intra_weights(const int* y, const float* S_own, int ld_s, const float* rkey, const unsigned char* rand_flag, float* w, int P, void* stream);
 /* the same sampling over the GLOBAL batch under data parallelism (the reference runs :302-334 on the gathered batch):
- * intra_pack writes this rank's records rec[3][P] = {label (int bits), own-class similarity, random key}; after an
+ * nce_records (below) writes this rank's records rec[3][P] = {label (int bits), own-class similarity, random key}; after an
  * all-gather rank r's block lies at rec + r*rank_stride and intra_weights_global returns this rank's weights, multiplied by `scale`
  * (= ranks when the gradient all-reduce averages). */
-int wseg_intra_pack(const int* y, const float* S_own, const float* rkey, float* rec, int P, void* stream);
 int wseg_intra_weights_global(const float* rec, float* w, int P, int ranks, int own_rank, float scale, long rank_stride, void* stream);
-int wseg_nce_loss_grad(const float* fn, const float* nrm, const float* S_own, const float* S_oth, const int* y_own, const int* y_oth,
-                       const float* w_intra, const float* p_own, const float* p_oth, float* dF, float* sums, int P,
-                       float coef_cross, float coef_intra, void* stream);
 
-/* ---- fused pixel-to-prototype contrast: the product path of contrast_train.py:245-334 (nce_sims / nce_loss_grad above are its
- * unfused reference formulation).  Two launches per step serve BOTH views; the normalised features and the [P,21] similarity rows
+/* ---- fused pixel-to-prototype contrast, contrast_train.py:245-334 (csrc/nce.hip).
+ * Two launches per step serve BOTH views; the normalised features and the [P,21] similarity rows
  * never reach HBM: every launch reads the raw features once (P*128*4 B) and writes only records (12 B / pixel) or dF (P*128*4 B).
  *   nce_records : rec[3][P] = {label (int bits), similarity of the pixel to its OWN class's prototype of p_own, rkey (when given)} — what the
  *                 hard-pixel sampling (intra_weights / the all-gather + intra_weights_global) needs; fields used: F, p_own, y_own, rkey, rec
@@ -316,7 +311,7 @@ typedef struct {
   float* rec;            /* [3][P] out (nce_records) */
   float* dF;             /* [P][128] out (nce_fused) */
 } wseg_nce_view;
-/* nce_records, split_bf16 = 0: exact-f32 MFMA (the fp32 parity mode: the record's similarity is bit-identical to the one nce_fused uses);
+/* nce_records, split_bf16 = 0: exact-f32 MFMA (the fp32 parity mode: the record's similarity comes from the same nce_sims16 arithmetic as the one nce_fused uses);
  * 1: split-bf16 products (hi.hi + lo.hi + hi.lo on the bf16 MFMA, 16-17 operand bits; the bf16 and bf16x3 modes — the similarity only RANKS pixels) */
 int wseg_nce_records(const wseg_nce_view* views, int nviews, int P, int split_bf16, void* stream);
 int wseg_nce_fused(const wseg_nce_view* views, int nviews, int P, float coef_cross, float coef_intra, float* sums /* [3], accumulated */, void* stream);

@@ -520,59 +520,6 @@ def test_lookahead_prefix_dropped_when_frozen_state_changes(proc_sd):
         assert abs(outs[0][k] - outs[1][k]) <= 5e-5 * max(1.0, abs(outs[0][k])), (k, outs[0][k], outs[1][k])
 
 
-@pytest.mark.parametrize("P", [4096, 1000, 300007])
-def test_fused_nce_matches_the_unfused_formulation(P):
-    """csrc/loss.hip nce_records + nce_fused (the product path: both views in one launch, nothing but records / dF written)
-    against the unfused reference formulation nce_sims -> intra_pack -> nce_loss_grad on the same inputs: the records and dF
-    bit for bit (same MFMA arithmetic), the three loss sums up to the order of the float atomics.  P = 1000: row tails;
-    P = 300007: every wave of the record pass walks 4-5 tiles (its two-tiles-in-flight pipeline in steady state, odd and even trip counts)."""
-    from wseg_amd import _lib as L
-    dev = "cuda"
-    g = torch.Generator().manual_seed(P)
-    V = []
-    for i in range(2):
-        F = torch.randn(P, 128, generator=g)
-        F[5] = 0.0                                       # a dead pixel: zero feature row (F.normalize eps path)
-        V.append(dict(F=F.to(dev), p=torch.nn.functional.normalize(torch.randn(21, 128, generator=g), dim=1).to(dev),
-                      y=torch.randint(0, 21, (P,), generator=g, dtype=torch.int32).to(dev),
-                      w=((torch.rand(P, generator=g) < 0.4).float() * torch.rand(P, generator=g) / P).to(dev),
-                      rkey=torch.rand(P, generator=g).to(dev)))
-    cc, ci = 0.1 / (2 * P), 0.05
-    ref_sums = torch.zeros(3, device=dev)
-    for v, o in ((V[0], V[1]), (V[1], V[0])):
-        v["fn"], v["nrm"] = torch.empty(P, 128, device=dev), torch.empty(P, device=dev)
-        v["So"], v["St"] = torch.empty(P, 21, device=dev), torch.empty(P, 21, device=dev)
-        L.nce_sims(v["F"], v["p"], o["p"], v["fn"], v["nrm"], v["So"], v["St"], P)
-        v["rec_ref"] = torch.empty(3, P, device=dev)
-        L.intra_pack(v["y"], v["So"], v["rkey"], v["rec_ref"], P)
-        v["dF_ref"] = torch.empty(P, 128, device=dev)
-        L.nce_loss_grad(v["fn"], v["nrm"], v["So"], v["St"], v["y"], o["y"], v["w"], v["p"], o["p"], v["dF_ref"], ref_sums, P, cc, ci)
-    for v in V:
-        v["rec"], v["dF"] = torch.full((3, P), float("nan"), device=dev), torch.full((P, 128), float("nan"), device=dev)
-    L.nce_records([dict(F=v["F"], p_own=v["p"], y_own=v["y"], rkey=v["rkey"], rec=v["rec"]) for v in V], P)
-    sums = torch.zeros(3, device=dev)
-    L.nce_fused([dict(F=v["F"], p_own=v["p"], p_oth=o["p"], y_own=v["y"], y_oth=o["y"], w_intra=v["w"], dF=v["dF"]) for v, o in ((V[0], V[1]), (V[1], V[0]))],
-                P, cc, ci, sums)
-    for v in V:
-        assert torch.equal(v["rec"].view(torch.int32), v["rec_ref"].view(torch.int32))
-        assert torch.equal(v["dF"], v["dF_ref"])
-        assert torch.isfinite(v["dF"]).all()
-    assert torch.allclose(sums, ref_sums, rtol=2e-6, atol=0), (sums, ref_sums)
-    assert float(ref_sums.abs().min()) > 0
-    # split-bf16 form of the record pass (bf16 / bf16x3 modes): labels and keys identical, similarities to 3e-6
-    rec3 = [torch.empty(3, P, device=dev) for _ in V]
-    L.nce_records([dict(F=v["F"], p_own=v["p"], y_own=v["y"], rkey=v["rkey"], rec=r) for v, r in zip(V, rec3)], P, split_bf16=True)
-    for v, r in zip(V, rec3):
-        assert torch.equal(r[0].view(torch.int32), v["rec_ref"][0].view(torch.int32)) and torch.equal(r[2], v["rec_ref"][2])
-        assert float((r[1] - v["rec_ref"][1]).abs().max()) <= 3e-6
-    # the records feed the sort-based sampler through a leading dimension of 1 exactly as the [P,21] table did through 21
-    if P > 8192: return                              # (the single-rank sampler sorts one view in LDS: P <= 8192)
-    w21, w1 = torch.empty(P, device=dev), torch.empty(P, device=dev)
-    L.intra_weights(V[0]["y"], V[0]["So"], V[0]["rkey"], None, w21, P)
-    L.intra_weights(V[0]["y"], V[0]["rec"][1], V[0]["rkey"], None, w1, P, ld_s=1)
-    assert torch.equal(w21, w1)
-
-
 @pytest.mark.parametrize("ranks", [1, 2, 8])
 def test_intra_weights_global_matches_sorted_kernel(ranks):
     """Hard-pixel sampling over the gathered batch (radix-select thresholds on the all-gathered records, one workgroup per class)
@@ -580,24 +527,14 @@ def test_intra_weights_global_matches_sorted_kernel(ranks):
     ranks = 8: the world size of BASELINE config 3 (P = 1024 per rank here: the sort-based reference kernel holds at most 8192 pixels)."""
     from wseg_amd import _lib as L
     dev = "cuda"
-    P = 1536 if ranks < 8 else 1024
-    g = torch.Generator().manual_seed(11 + ranks)
+    from .test_gpu_loss_kernels import sampling_inputs
+    P, y, S, rk = sampling_inputs(ranks)
     PG = P * ranks
-    y = torch.randint(0, 21, (PG,), generator=g, dtype=torch.int32)
-    y[y == 7] = 3                                   # an absent class
-    y[5] = 19; y[y == 19] = 2; y[5] = 19            # a class with a single pixel (skipped, still counted)
-    S = (torch.rand(PG, 21, generator=g) * 2 - 1)
-    S[10:40, :] = S[9, :]                           # tied similarities: order falls back to the pixel index
-    y[10:40] = y[9]
-    rk = torch.rand(PG, generator=g)
-    rk[100:120] = rk[99]
+    # every rank's record block [3][P] = {label bits, similarity to the pixel's own class, random key}
+    rec = torch.stack([y.view(torch.float32).view(ranks, P), S.gather(1, y.long()[:, None]).view(ranks, P), rk.view(ranks, P)], 1).to(dev)
     y, S, rk = y.to(dev), S.to(dev), rk.to(dev)
     w_ref = torch.empty(PG, device=dev)
     L.intra_weights(y, S, rk, None, w_ref, PG)
-    rec = torch.empty(ranks, 3, P, device=dev)
-    for r in range(ranks):
-        sl = slice(r * P, (r + 1) * P)
-        L.intra_pack(y[sl].contiguous(), S[sl].contiguous(), rk[sl].contiguous(), rec[r], P)
     for r in range(ranks):
         w = torch.empty(P, device=dev)
         L.intra_weights_global(rec, w, P, ranks, r, float(ranks), 3 * P)

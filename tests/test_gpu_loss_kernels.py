@@ -1,12 +1,13 @@
-"""GPU: the loss-phase kernels one entry point at a time (csrc/maps.hip, the non-NCE half of csrc/loss.hip, the planar
-resizes of csrc/head.hip) against float64 CPU references of the same operation.
+"""GPU: the loss-phase kernels one entry point at a time (csrc/maps.hip, csrc/loss.hip, csrc/nce.hip, the planar resizes of
+csrc/head.hip) against float64 CPU references of the same operation.
 
 How the bars are set: every tolerance is derived from the kernel's arithmetic, never fitted to a run.
   u = 2^-24, the unit roundoff of f32.  A sum of m f32 terms accumulated in a serial chain of length c has error
   <= c * u * sum|terms|; every bar below states its chain and carries a safety factor of 2.
 Decisions (arg-max / arg-min, top-k membership, max_onehot, pseudo-label arg-max) are not arithmetic: the arithmetic is
 compared under the kernel's own decisions, and every decision that differs from the float64 one is asserted to be a
-near-tie of the float64 values within the derived value bar.  Exact ties are built from dyadic values (multiples of
+near-tie of the float64 values within the derived value bar (where the kernel does not return its decision — the rank band
+of nce_fused — the pixels whose float64 values are such near-ties are left out, and their share is capped).  Exact ties are built from dyadic values (multiples of
 1/64 on grids whose interpolation weights are multiples of 1/16), where f32 and float64 agree bit for bit, and the
 stated tie rule is asserted exactly.
 """
@@ -805,3 +806,220 @@ def test_proto_non_finite_values(n):
     others = [c for c in range(21) if c not in (3, 4, 5)]
     assert torch.equal(pc[others], p0.cpu()[others])
     assert bool(torch.isfinite(pc[4]).all())
+
+
+# ------------------------------------------------------------------------------------------------ pixel-to-prototype contrast (nce.hip)
+# delta S, the error of one f32 similarity against normalize(F) . p in float64 (|S| <= 1): the row norm is a 32-term lane chain plus
+# two shuffles (34), the contraction a chain of at most 128 MFMA partial sums with sum|terms| <= |F| |p| = |F| (Cauchy-Schwarz; the
+# prototypes are unit vectors), scaled by 1 / |F|.  S_ERR is the raw figure, S_BAR the bar (the safety factor applied once).
+S_ERR = (128 + 34) * U32
+S_BAR = SAFETY * S_ERR                       # 1.9e-5
+ITAU = 10.0                                  # 1 / tau, tau = 0.1
+NCE_CI = 0.05                                # coef_intra; coef_cross = 0.1 / (2 P) (the step's values at world 1)
+NCE_MAX_EXCLUDED = 0.02                      # share of pixels per view whose rank band 3..12 may be undecided at S_BAR
+
+
+def _nce_reference(V, cc, ci, with_grad):
+    """float64 restatement of contrast_train.py:245-334 for both views (tau = 0.1): per view the per-pixel cross-prototype,
+    cross-pseudo-label and intra-view terms, the rank band, and (with_grad) dF through the F.normalize backward with the
+    elementwise error bar of the kernel's chain.  V[i]: F, p, y, w (f32 / int CPU tensors); w is used as given."""
+    out = []
+    for v, o in ((V[0], V[1]), (V[1], V[0])):
+        P = v["F"].shape[0]
+        F64 = v["F"].double()
+        nr = F64.norm(dim=1, keepdim=True)
+        fn = F64 / nr.clamp_min(1e-12)
+        Po, Pt = v["p"].double(), o["p"].double()
+        So, St = fn @ Po.T, fn @ Pt.T
+        yo, yt = v["y"].long()[:, None], o["y"].long()[:, None]
+        # semi-hard negatives: similarity ranks 3..12, descending, the lower class first on a tie (:293-294)
+        srt, order = torch.sort(So, dim=1, descending=True, stable=True)
+        neg = torch.zeros(P, 21, dtype=torch.float64).scatter_(1, order[:, 3:13], 1.0)
+        gap = torch.minimum(srt[:, 2] - srt[:, 3], srt[:, 12] - srt[:, 13])
+        dead = nr[:, 0] == 0                                  # S == 0 exactly on both sides: the stated tie rule decides, exactly
+        r = dict(So=So, yo=yo, undecided=(gap < 2 * S_BAR) & ~dead, dead=dead)
+        Eo, Et = torch.exp(ITAU * So), torch.exp(ITAU * St)
+        oh_yo = torch.zeros(P, 21, dtype=torch.float64).scatter_(1, yo, 1.0)
+        oh_yt = torch.zeros(P, 21, dtype=torch.float64).scatter_(1, yt, 1.0)
+        m = neg + oh_yo                                       # the positive, and the band (the positive again if it lies inside)
+        a2 = (m * Eo).sum(1, keepdim=True)
+        sig_o, sig_t, q = Eo / Eo.sum(1, keepdim=True), Et / Et.sum(1, keepdim=True), m * Eo / a2
+        r["L"] = (-torch.log(sig_t.gather(1, yo))[:, 0], -torch.log(sig_o.gather(1, yt))[:, 0], -torch.log(Eo.gather(1, yo) / a2)[:, 0])
+        if with_grad:
+            w = v["w"].double()[:, None]
+            kc, ki = cc * ITAU, ci * ITAU * w
+            dSo = kc * (sig_o - oh_yt) + ki * (q - oh_yo)
+            dSt = kc * (sig_t - oh_yo)
+            dfn = dSo @ Po + dSt @ Pt
+            dot = (dfn * fn).sum(1, keepdim=True)
+            inv = torch.where(dead[:, None], torch.zeros((), dtype=torch.float64), 1.0 / nr.clamp_min(1e-300))
+            r["dF"] = (dfn - fn * dot) * inv
+            # ---- the bar of dF, term by term (raw errors; SAFETY once at the end)
+            # e = expf(10 S): the product rounds (10 u on the exponent), expf 2 u -> 12 u relative; a softmax entry s = e / sum: 12 u
+            # + (12 + 21) u of the 21-term sum + 1 u of the division = 46 u relative; through delta S it moves by
+            # sum_j |ds/dS_j| S_ERR = 10 s * 2 (1 - s) S_ERR <= 20 s S_ERR.  The same holds for q (entries sum to 1, <= 13 terms).
+            # dS = kc (s - [c == y]) + ki (q - [c == y]): each difference 1 rounding, kc 1 and ki 2 roundings and their products 1
+            # each (<= 4 u of the term), the final add 1 u of dS.
+            rel = 20 * S_ERR + 46 * U32
+            e_dSo = rel * (kc * sig_o + ki * q) + 4 * U32 * (kc * (sig_o - oh_yt).abs() + ki * (q - oh_yo).abs()) + U32 * dSo.abs()
+            e_dSt = rel * kc * sig_t + 5 * U32 * dSt.abs()
+            # d fn = dS . P: a chain of 44 MFMA terms on sum |dS| |P|
+            e_dfn = e_dSo @ Po.abs() + e_dSt @ Pt.abs() + 44 * U32 * (dSo.abs() @ Po.abs() + dSt.abs() @ Pt.abs())
+            # fn = F * (1 / |F|): the norm 17 u (half of the 34-chain of its square) + sqrt, reciprocal, product: 20 u, the product
+            # 1 u more; dot = sum_128 dfn fn: 32 products per lane + 2 shuffles (34) and 1 u per product
+            e_dot = (e_dfn * fn.abs()).sum(1, keepdim=True) + (21 + 35) * U32 * (dfn * fn).abs().sum(1, keepdim=True)
+            # dF = (dfn - fn dot) * inv: fn dot carries fn's 21 u and 1 u, the difference 1 u, inv 20 u and the product 1 u
+            bar = inv * (e_dfn + fn.abs() * e_dot + 22 * U32 * (fn * dot).abs()) + 22 * U32 * r["dF"].abs()
+            r["dF_bar"] = SAFETY * bar
+        out.append(r)
+    return out
+
+
+def _nce_sum_bar(L, weight, P):
+    """|sum_f32 - sum_64| of one loss sum = sum_p weight_p L_p.  Per pixel L = -log(e_y / sum_c e_c) moves by 20 S_ERR through delta S
+    (sum_c |dL/dS_c| = 10 * 2 (1 - s_y) <= 20), by (12 + 12 + 21 + 1) u through exp / sum / division into the log, and by 2 u |L| (logf, the
+    coefficient).  The accumulation: `trips` serial adds per lane, a 6-level wave tree, 4 waves, one same-address atomic per workgroup."""
+    groups = 2 * ((P + 63) // 64)
+    blocks = min(2048, (groups + 3) // 4)
+    chain = math.ceil(groups / (4 * blocks)) + 6 + 4 + blocks
+    return SAFETY * float((weight * (20 * S_ERR + 46 * U32 + 2 * U32 * L.abs())).sum() + chain * U32 * (weight * L.abs()).sum())
+
+
+@pytest.fixture(scope="module", params=[77, 1000, 4096, 300007])
+def nce_case(request):
+    """Inputs of both views (the generators of the retired fused-vs-unfused test) and their float64 reference, built once per P.
+    P = 77: one partial 64-pixel group, partial 16-pixel tiles; 1000: tails in both group sizes; 4096: full groups; 300007: every
+    record-pass wave walks 4-5 tiles (the two-tiles-in-flight pipeline in steady state, odd and even trip counts)."""
+    P = request.param
+    g = _gen(P)
+    V = []
+    for _ in range(2):
+        Fv = torch.randn(P, 128, generator=g)
+        Fv[5] = 0.0                                          # a dead pixel: zero feature row (the F.normalize eps path)
+        V.append(dict(F=Fv, p=F.normalize(torch.randn(21, 128, generator=g), dim=1),
+                      y=torch.randint(0, 21, (P,), generator=g, dtype=torch.int32),
+                      w=(torch.rand(P, generator=g) < 0.4).float() * torch.rand(P, generator=g) / P,
+                      rkey=torch.rand(P, generator=g)))
+    cc = 0.1 / (2 * P)
+    with_grad = P <= 8192                                    # (P = 300007 compares records and loss sums only)
+    dec = _nce_reference(V, cc, NCE_CI, False)
+    for v, d in zip(V, dec):
+        v["w"] = torch.where(d["undecided"], torch.zeros(()), v["w"])       # the intra term covers the decided pixels only
+    ref = _nce_reference(V, cc, NCE_CI, True) if with_grad else dec
+    return dict(P=P, V=V, cc=cc, ref=ref, with_grad=with_grad)
+
+
+def _dev_views(V):
+    return [{k: t.to(DEV) for k, t in v.items()} for v in V]
+
+
+def test_nce_records(nce_case):
+    """rec[3][P] = {label bits, similarity to the pixel's own class, random key}: labels and keys exact, the similarity within S_BAR of
+    float64; the split-bf16 form (operands x = hi + lo to 16-17 bits) within 3e-6 of the exact record, the bar it has always been held
+    to; without keys the same labels and similarities, bit for bit."""
+    L = _L()
+    P, V, ref = nce_case["P"], nce_case["V"], nce_case["ref"]
+    D = _dev_views(V)
+    rec = [torch.full((3, P), float("nan"), device=DEV) for _ in D]
+    L.nce_records([dict(F=d["F"], p_own=d["p"], y_own=d["y"], rkey=d["rkey"], rec=r) for d, r in zip(D, rec)], P)
+    rec3 = [torch.full((3, P), float("nan"), device=DEV) for _ in D]
+    L.nce_records([dict(F=d["F"], p_own=d["p"], y_own=d["y"], rkey=d["rkey"], rec=r) for d, r in zip(D, rec3)], P, split_bf16=True)
+    rec0 = [torch.full((3, P), float("nan"), device=DEV) for _ in D]
+    L.nce_records([dict(F=d["F"], p_own=d["p"], y_own=d["y"], rec=r) for d, r in zip(D, rec0)], P)
+    for i, (v, r) in enumerate(zip(V, ref)):
+        rc, r3, r0 = rec[i].cpu(), rec3[i].cpu(), rec0[i].cpu()
+        assert torch.equal(rc[0].view(torch.int32), v["y"]) and torch.equal(rc[2], v["rkey"])
+        s64 = r["So"].gather(1, r["yo"])[:, 0]
+        err = (rc[1].double() - s64).abs()
+        assert float(err.max()) <= S_BAR, f"view {i}: max |dS| {float(err.max()):.3e} (bar {S_BAR:.3e})"
+        assert float(rc[1, 5]) == 0.0                                            # the dead pixel: exactly 0
+        assert torch.equal(r3[0].view(torch.int32), v["y"]) and torch.equal(r3[2], v["rkey"])
+        assert float((r3[1] - rc[1]).abs().max()) <= 3e-6
+        assert torch.equal(r0[:2].view(torch.int32), rc[:2].view(torch.int32)) and bool(torch.isnan(r0[2]).all())
+    if P > 8192:
+        return                                               # (the single-rank sampler sorts one view in LDS: P <= 8192)
+    # the records feed the sort-based sampler through a leading dimension of 1 exactly as a [P,21] table does through 21
+    table = torch.zeros(P, 21, device=DEV)
+    table[torch.arange(P, device=DEV), D[0]["y"].long()] = rec[0][1]
+    w21, w1 = torch.empty(P, device=DEV), torch.empty(P, device=DEV)
+    L.intra_weights(D[0]["y"], table, D[0]["rkey"], None, w21, P)
+    L.intra_weights(D[0]["y"], rec[0][1], D[0]["rkey"], None, w1, P, ld_s=1)
+    assert torch.equal(w21, w1) and float(w1.sum()) > 0
+
+
+def test_nce_fused(nce_case):
+    """The three loss sums and dF of both views against float64.  The rank band 3..12 is a decision: a pixel whose float64 gap at rank
+    2/3 or 12/13 is below 2 S_BAR carries no intra weight and is left out of the dF comparison (at most 2 % per view); the cross terms
+    do not depend on the band and cover every pixel."""
+    L = _L()
+    P, V, ref, cc = nce_case["P"], nce_case["V"], nce_case["ref"], nce_case["cc"]
+    share = [float(r["undecided"].double().mean()) for r in ref]
+    assert max(share) <= NCE_MAX_EXCLUDED, f"P={P}: excluded share per view {share[0]:.4%}, {share[1]:.4%}"
+    D = _dev_views(V)
+    dF = [torch.full((P, 128), float("nan"), device=DEV) for _ in D]
+    sums = torch.zeros(3, device=DEV)
+    L.nce_fused([dict(F=d["F"], p_own=d["p"], p_oth=o["p"], y_own=d["y"], y_oth=o["y"], w_intra=d["w"], dF=g)
+                 for d, o, g in ((D[0], D[1], dF[0]), (D[1], D[0], dF[1]))], P, cc, NCE_CI, sums)
+    got = sums.cpu().double()
+    for k in range(3):
+        wts = [torch.full((P,), cc, dtype=torch.float64) if k < 2 else NCE_CI * v["w"].double() for v in V]
+        want = sum(float((w * r["L"][k]).sum()) for w, r in zip(wts, ref))
+        bar = _nce_sum_bar(torch.cat([r["L"][k] for r in ref]), torch.cat(wts), P)
+        assert want > 0 and float(got[k]) != 0.0
+        assert abs(float(got[k]) - want) <= bar, f"P={P} sum {k}: {float(got[k]):.9g} vs {want:.9g}, bar {bar:.3e} (excluded {share[0]:.4%}, {share[1]:.4%})"
+    for i, r in enumerate(ref):
+        g = dF[i].cpu()
+        assert bool(torch.isfinite(g).all())
+        assert bool((g[5] == 0).all())                                           # the dead pixel: inv = 0, the gradient is exactly 0
+        if not nce_case["with_grad"]:
+            continue
+        keep = ~r["undecided"]
+        err = (g.double() - r["dF"]).abs()[keep]
+        over = err - r["dF_bar"][keep]
+        assert float(over.max()) <= 0, (f"P={P} view {i}: max err {float(err.max()):.3e}, worst excess {float(over.max()):.3e} over a bar of "
+                                        f"{float(r['dF_bar'][keep].view(-1)[over.argmax()]):.3e} (excluded {share[i]:.4%})")
+
+
+# ------------------------------------------------------------------------------------------------ hard-pixel sampling
+def sampling_inputs(ranks):
+    """Labels, a [PG,21] similarity table and random keys of a gathered batch: an absent class, a single-pixel class, tied similarities
+    and tied keys (the order falls back to the pixel index).  P = 1024 per rank at 8 ranks: the sort-based kernel holds 8192 pixels."""
+    P = 1536 if ranks < 8 else 1024
+    g = _gen(11 + ranks)
+    PG = P * ranks
+    y = torch.randint(0, 21, (PG,), generator=g, dtype=torch.int32)
+    y[y == 7] = 3                                   # an absent class
+    y[5] = 19; y[y == 19] = 2; y[5] = 19            # a class with a single pixel (skipped, still counted)
+    S = (torch.rand(PG, 21, generator=g) * 2 - 1)
+    S[10:40, :] = S[9, :]                           # tied similarities: order falls back to the pixel index
+    y[10:40] = y[9]
+    rk = torch.rand(PG, generator=g)
+    rk[100:120] = rk[99]
+    return P, y, S, rk
+
+
+def test_intra_weights_against_the_sampling_rule():
+    """contrast_train.py:302-331 restated on integers: per class with len >= 2 the random half (the len // 2 smallest keys) and the
+    similarity rank band [int(0.6 len) - len // 2, int(0.6 len)), ties ordered by pixel index; weight = selections / (2 (len // 2) C),
+    C = classes present.  An integer rule on f32 keys: exact up to the kernel's one f32 division (rtol 1e-6)."""
+    L = _L()
+    P, y, S, rk = sampling_inputs(1)
+    w = torch.empty(P, device=DEV)
+    L.intra_weights(y.to(DEV), S.to(DEV), rk.to(DEV), None, w, P)
+    yn, rkn = y.numpy(), rk.numpy()
+    sim = S.numpy()[np.arange(P), yn]
+    ref = np.zeros(P)
+    present = np.unique(yn)
+    assert 7 not in present and int((yn == 19).sum()) == 1
+    for c in present:
+        idx = np.nonzero(yn == c)[0]                          # ascending pixel index: a stable sort keeps it among equal keys
+        n = len(idx)
+        if n < 2:
+            continue
+        half, kk = n // 2, int(n * 0.6)
+        unit = 1.0 / (2 * half * len(present))
+        ref[idx[np.argsort(rkn[idx], kind="stable")[:half]]] += unit
+        ref[idx[np.argsort(sim[idx], kind="stable")[kk - half:kk]]] += unit
+    got = w.cpu().double().numpy()
+    assert ref.sum() > 0 and (got[ref == 0] == 0).all()
+    np.testing.assert_allclose(got, ref, rtol=1e-6, atol=0)

@@ -353,12 +353,8 @@ def head_grad_fused(dF, d_cam_low, head, d_head, ld, N, ih, iw, oh, ow): _call("
 def pseudo_label(R, label20, bg_thr, y, ncam, N, npix): _call("wseg_pseudo_label", _v(R), _v(label20), _f(bg_thr), _v(y), _v(ncam), N, npix)
 def proto_candidates(ncam, F, tie_idx, cand_val, cand_feat, cand_const, N, npix, K): _call("wseg_proto_candidates", _v(ncam), _v(F), _v(tie_idx), _v(cand_val), _v(cand_feat), _v(cand_const), N, npix, K)
 def proto_merge(cand_val, cand_feat, cand_const, protos, world, K, rank_stride=0): _call("wseg_proto_merge", _v(cand_val), _v(cand_feat), _v(cand_const), _v(protos), world, K, C.c_long(rank_stride))
-def nce_sims(F, p_own, p_oth, fn, nrm, S_own, S_oth, P): _call("wseg_nce_sims", _v(F), _v(p_own), _v(p_oth), _v(fn), _v(nrm), _v(S_own), _v(S_oth), P)
 def intra_weights(y, S_own, rkey, rand_flag, w, P, ld_s=21): _call("wseg_intra_weights", _v(y), _v(S_own), ld_s, _v(rkey), _v(rand_flag), _v(w), P)
-def intra_pack(y, S_own, rkey, rec, P): _call("wseg_intra_pack", _v(y), _v(S_own), _v(rkey), _v(rec), P)
 def intra_weights_global(rec, w, P, ranks, own_rank, scale, rank_stride): _call("wseg_intra_weights_global", _v(rec), _v(w), P, ranks, own_rank, _f(scale), C.c_long(rank_stride))
-def nce_loss_grad(fn, nrm, S_own, S_oth, y_own, y_oth, w_intra, p_own, p_oth, dF, sums, P, coef_cross, coef_intra):
-    _call("wseg_nce_loss_grad", _v(fn), _v(nrm), _v(S_own), _v(S_oth), _v(y_own), _v(y_oth), _v(w_intra), _v(p_own), _v(p_oth), _v(dF), _v(sums), P, _f(coef_cross), _f(coef_intra))
 
 
 class NceView(C.Structure):

@@ -171,6 +171,7 @@ __global__ __launch_bounds__(256) void rw_pool_kernel(const float* __restrict__ 
 }
 
 // nn.Upsample(mode='bilinear') source index (align_corners=False): max(scale*(o+0.5)-0.5, 0), scale = in/out
+// (differs from loss_helpers.h src_index: half-pixel centres, and no clamp of i0, which cannot exceed in_size - 1 here)
 __device__ __forceinline__ void src_index(int o, float scale, int in_size, int& i0, int& i1, float& l1) {
   float s = scale * (o + 0.5f) - 0.5f;
   s = s < 0.f ? 0.f : s;

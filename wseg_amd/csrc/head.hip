@@ -55,6 +55,7 @@ __global__ void cam_gate_kernel(const float* __restrict__ cam, const float* __re
 }
 
 // ---- torch-compatible bilinear source index (area_pixel_compute_source_index)
+// (loss_helpers.h src_index / ac_scale are the align_corners=True case alone; here `align` is a run-time argument of the planar resizes)
 __device__ __forceinline__ void src_index(int o, float scale, bool align, int in_size, int& i0, int& i1, float& f) {
   float s = align ? scale * o : fmaxf(scale * (o + 0.5f) - 0.5f, 0.f);
   i0 = (int)s;

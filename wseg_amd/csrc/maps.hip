@@ -14,20 +14,10 @@
 // U is evaluated by ONE pinned expression (explicit fma/mul, no compiler contraction) so every kernel sees
 // bit-identical values (arg-max positions, `u > 0` gates and thresholds stay consistent between kernels).
 #include <algorithm>
-#include "common.h"
+#include "loss_helpers.h"
 
 namespace {
 
-__device__ __forceinline__ void src_index(int o, float scale, int in_size, int& i0, int& i1, float& f) {
-  const float s = scale * o;                       // align_corners=True
-  i0 = (int)s;
-  if (i0 > in_size - 1) i0 = in_size - 1;
-  i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-  f = s - i0;
-}
-__device__ __forceinline__ float ac_scale(int in_size, int out_size) {
-  return out_size > 1 ? (float)(in_size - 1) / (out_size - 1) : 0.f;
-}
 __device__ __forceinline__ float up_value(const float* __restrict__ p, int w, int y0, int y1, int x0, int x1, float fy, float fx) {
   const float a = __fmaf_rn(fx, p[y0 * w + x1], __fmul_rn(1.f - fx, p[y0 * w + x0]));
   const float b = __fmaf_rn(fx, p[y1 * w + x1], __fmul_rn(1.f - fx, p[y1 * w + x0]));
@@ -38,22 +28,46 @@ __device__ __forceinline__ float up_at(const float* __restrict__ p, int h, int w
   src_index(oy, sy, h, y0, y1, fy); src_index(ox, sx, w, x0, x1, fx);
   return up_value(p, w, y0, y1, x0, x1, fy, fx);
 }
-__device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  float t = 0.f;
-  for (int i = 0; i < nw; ++i) t += red[i];
-  return t;
-}
 // 256 threads sweep rows [r0, r1) of an S-wide image: `tpr` (power of two) threads per row
 __device__ __forceinline__ int threads_per_row(int S) { return S > 128 ? 256 : (S > 64 ? 128 : 64); }
 
-// ---- per-plane statistics of relu(U): stats[pl] = {mx, mn, sum(U), argmax, argmin, 0}; index order = hi-res row major.
-// A plane is split over `chunks` row ranges; partials meet in packed 64-bit atomics (see loss.hip plane_stats).
+// ---- per-plane statistics: max/min of relu(U) with their first index, sum of U:  stats[pl] = {mx, mn, sum, (float)argmax, (float)argmin, 0}
+// Two families share the workspace layout, the keys and the final kernel: plane_stats reads materialised planes U [planes][npix] (inference), up_plane_stats evaluates
+// U from the low-resolution plane (the training step).  A plane is split over `chunks` workgroups; partials meet in packed 64-bit atomics:
+//   max key = (bits(relu) << 32) | ~index   (atomicMax: largest value, then lowest index)
+//   min key = (bits(relu) << 32) |  index   (atomicMin: smallest value, then lowest index)   (relu >= 0: bits are ordered)
+__global__ __launch_bounds__(256) void plane_stats_partial_kernel(const float* __restrict__ U, unsigned long long* __restrict__ kmax,
+                                                                  unsigned long long* __restrict__ kmin, float* __restrict__ ksum,
+                                                                  int npix, int chunks) {
+  __shared__ unsigned long long s_mx[256], s_mn[256];
+  __shared__ float s_sum[256];
+  const int pl = blockIdx.x / chunks, ck = blockIdx.x - pl * chunks, tid = threadIdx.x;
+  const float* p = U + (size_t)pl * npix;
+  const int per = (npix + chunks - 1) / chunks;
+  const int i0 = ck * per, i1 = min(npix, i0 + per);
+  unsigned long long mx = 0ull, mn = ~0ull;
+  float sum = 0.f;
+  for (int i = i0 + tid; i < i1; i += 256) {
+    const float u = p[i];
+    const unsigned rb = __float_as_uint(fmaxf(u, 0.f));
+    sum += u;
+    const unsigned long long a = ((unsigned long long)rb << 32) | (unsigned)(~i), b = ((unsigned long long)rb << 32) | (unsigned)i;
+    mx = a > mx ? a : mx; mn = b < mn ? b : mn;
+  }
+  s_mx[tid] = mx; s_mn[tid] = mn; s_sum[tid] = sum;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) {
+      if (s_mx[tid + o] > s_mx[tid]) s_mx[tid] = s_mx[tid + o];
+      if (s_mn[tid + o] < s_mn[tid]) s_mn[tid] = s_mn[tid + o];
+      s_sum[tid] += s_sum[tid + o];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) { atomicMax(&kmax[pl], s_mx[0]); atomicMin(&kmin[pl], s_mn[0]); atomicAdd(&ksum[pl], s_sum[0]); }
+}
+
+// ---- the same statistics of relu(U) evaluated on the fly; index order = hi-res row major.  A plane is split over `chunks` row ranges.
 __global__ __launch_bounds__(256) void up_stats_partial_kernel(const float* __restrict__ low, unsigned long long* __restrict__ kmax,
                                                               unsigned long long* __restrict__ kmin, float* __restrict__ ksum,
                                                               int h, int w, int S, int chunks, const float* __restrict__ label20) {
@@ -140,6 +154,7 @@ __global__ void up_stats_init_kernel(unsigned long long* __restrict__ kmax, unsi
   const long pl = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (pl < planes) { kmax[pl] = 0ull; kmin[pl] = ~0ull; ksum[pl] = 0.f; }
 }
+// keys -> stats[pl][6], for both families
 __global__ void up_stats_final_kernel(const unsigned long long* __restrict__ kmax, const unsigned long long* __restrict__ kmin,
                                       const float* __restrict__ ksum, float* __restrict__ stats, long planes) {
   const long pl = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -335,6 +350,22 @@ __global__ __launch_bounds__(256) void up_maps_bwd_kernel(const float* __restric
 
 #define GRID1(total) dim3((unsigned)(((total) + 255) / 256)), dim3(256)
 #define ST ((hipStream_t)stream)
+
+extern "C" size_t wseg_plane_stats_workspace_bytes(long planes) { return (size_t)planes * 24; }
+extern "C" int wseg_plane_stats(const float* U, float* stats, long planes, int npix, void* workspace, void* stream) {
+  WSEG_CHECK(U && stats && workspace && planes > 0 && npix > 0, "plane_stats: bad arguments");
+  unsigned long long* kmax = (unsigned long long*)workspace;
+  unsigned long long* kmin = kmax + planes;
+  float* ksum = (float*)(kmin + planes);
+  (void)hipMemsetAsync(kmax, 0x00, sizeof(unsigned long long) * planes, ST);
+  (void)hipMemsetAsync(kmin, 0xFF, sizeof(unsigned long long) * planes, ST);
+  (void)hipMemsetAsync(ksum, 0x00, sizeof(float) * planes, ST);
+  const int chunks = std::max(1, std::min(std::min(64, (int)((long)npix / 8192)), (int)std::max(1L, 2048 / planes)));
+  hipLaunchKernelGGL(plane_stats_partial_kernel, dim3((unsigned)(planes * chunks)), dim3(256), 0, ST, U, kmax, kmin, ksum, npix, chunks);
+  hipLaunchKernelGGL(up_stats_final_kernel, dim3((unsigned)((planes + 255) / 256)), dim3(256), 0, ST, kmax, kmin, ksum, stats, planes);
+  WSEG_LAUNCH_CHECK();
+  return 0;
+}
 
 // workspace: planes * 24 bytes (wseg_plane_stats_workspace_bytes)
 extern "C" int wseg_up_plane_stats(const float* low, float* stats, long planes, int h, int w, int S, const float* label20, void* workspace, void* stream) {

@@ -9,7 +9,7 @@ Global-batch semantics under data parallelism: the per-class top-
 candidates (value + feature row) of every rank are all-gathered and merged, so every rank holds the
 prototypes the reference would compute over the whole batch (one all-gather for both views); hard-pixel sampling (contrast_train.py
 :302-331) exchanges one {label, similarity, random key} record per pixel, and every rank finds the same
-global per-class order statistics (csrc/loss.hip intra_weights_global).
+global per-class order statistics (csrc/nce.hip intra_weights_global).
 """
 import os
 
@@ -273,7 +273,7 @@ def step(model, img1, img2, label20, bg_threshold=0.20, rng=None, rng_parity=Fal
     # record pass (similarities that only RANK pixels): exact-f32 MFMA in fp32 mode, split-bf16 products in the bf16 / bf16x3 modes
     nce_x3 = model.precision != "fp32"
     # ONE launch for both views: per-pixel records {label, similarity to the pixel's own-class prototype, random key} straight from
-    # the raw features (csrc/loss.hip nce_records): the inputs of the hard-pixel sampling.  Over the GLOBAL batch under data
+    # the raw features (csrc/nce.hip nce_records): the inputs of the hard-pixel sampling.  Over the GLOBAL batch under data
     # parallelism (the reference samples on the gathered batch): the records (96 KB per rank for both views) are
     # all-gathered, every rank finds the same global per-class order statistics and keeps the weights of its own pixels, scaled
     # by `world` because the gradient all-reduce averages.
@@ -304,7 +304,7 @@ def step(model, img1, img2, label20, bg_threshold=0.20, rng=None, rng_parity=Fal
         side[1].wait_event(ecr_done)
         _maps_backward_rv(v2, label20, N)
     main.wait_event(w2_done)
-    # similarities, the three InfoNCE terms and dF of BOTH views in one launch (csrc/loss.hip nce_fused): features read once, only dF written
+    # similarities, the three InfoNCE terms and dF of BOTH views in one launch (csrc/nce.hip nce_fused): features read once, only dF written
     for v in views:
         v.dF = _f32(P, 128, dev=dev)
     L.nce_fused([dict(F=v.F, p_own=v.protos, p_oth=o.protos, y_own=v.y, y_oth=o.y, w_intra=v.w_intra, dF=v.dF) for v, o in ((v1, v2), (v2, v1))],
