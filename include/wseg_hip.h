@@ -379,6 +379,25 @@ int wseg_rw_pool(const float* cams, const int* src, float bg, float* pooled, int
  * cropped to [H][W] (aff_infer.py:110-139): pred uint8 [H][W].  planes <= 32. */
 int wseg_rw_finish(const float* cam_rw, unsigned char* pred, int planes, int dh, int dw, int H, int W, void* stream);
 
+/* ---- AffinityNet training loss (aff_train.py:111-119 on network/resnet38_aff.py:57-63) and its gradient on the feature rows ----------
+ * label: uint8 [N][h][w] device, 0 background, 1..20 a class, 255 ignore.  Per pair (from f, to t) the indicators of voc12/data.py:170-199:
+ *   valid = label[f] < 255 && label[t] < 255;  bg = equal && label[f] == 0;  fg = equal && label[f] != 0 && valid;  neg = !equal && valid.
+ * feat: pixel rows [N*h*w][ld] in `dtype` (f32 or bf16; C % 8 == 0, C <= 512, ld >= C, ld % 8 == 0).
+ * out7 (f32 device): loss, bg_loss, fg_loss, neg_loss, bg_cnt, fg_cnt, neg_cnt with cnt = float(pairs) + 1e-5f, x_loss = sum / cnt over
+ *   the terms -log(aff + 1e-5) (bg, fg) / -log(1.00001 - aff) (neg), loss = bg/4 + fg/4 + neg/2.  No atomics: term sums per wave in f32,
+ *   per workgroup through LDS, then one workgroup in f64 in a fixed order; the pair counts are integers throughout.  The seven values
+ *   are bit-identical from run to run; a label map without a valid pair gives 0, 0, 0, 0, 1e-5, 1e-5, 1e-5.
+ * Every argument check runs before the first device call. */
+long wseg_aff_loss_workspace_bytes(int N, int h, int w, int radius);      /* -1 (and wseg_last_error) for a bad geometry */
+/* aff: [N][P][n_from] f32 as wseg_aff_pairs writes it, or NULL for a loss-only call (the backward needs it). */
+int wseg_aff_loss_forward(const void* feat, int ld, int C, const unsigned char* label, float* aff, void* workspace, float* out7, int N,
+                          int h, int w, int radius, int dtype, void* stream);
+/* d_feat[N*h*w][ld_d] f32 = gscale * d out7[0] / d feat (gscale: one f32 on the device, NULL = 1; out7 is read on the device as well).
+ * One wave per pixel gathers the pairs it belongs to in a fixed order: columns < C of EVERY row are written (zeros where a pixel is in
+ * no valid pair), columns >= C are untouched; a channel on which the two rows of a pair tie gets no contribution (sign(0) = 0). */
+int wseg_aff_loss_backward(const void* feat, int ld, int C, const unsigned char* label, const float* aff, const float* out7,
+                           const float* gscale, float* d_feat, int ld_d, int N, int h, int w, int radius, int dtype, void* stream);
+
 /* ---- fully connected CRF, mean field with exact Gaussian kernels (contrast_infer.py:102-134 --out_crf, aff_prepare.py:34-50) ----------
  * The reference calls pydensecrf, whose filters are a permutohedral-lattice approximation; these entry points evaluate every pair
  * (DESIGN.md §3 "crf" states the update).  One image of N = H*W pixels (pixel i = y*W + x), M labels, S label sets sharing the image.

@@ -440,6 +440,18 @@ def rw_pool(cams, src, bg, pooled, H, W, dh, dw):
 def rw_finish(cam_rw, pred, planes, dh, dw, H, W): _call("wseg_rw_finish", _v(cam_rw), _v(pred), planes, dh, dw, H, W)
 
 
+
+# ---------------------------------------------------------------------------------------------- AffinityNet training loss (csrc/aff_loss.hip)
+lib.wseg_aff_loss_workspace_bytes.restype = C.c_long
+
+
+def aff_loss_workspace_bytes(N, h, w, radius): return int(lib.wseg_aff_loss_workspace_bytes(N, h, w, radius))
+def aff_loss_forward(feat, ld, C_, label, aff, ws, out7, N, h, w, radius, dtype=None):
+    _call("wseg_aff_loss_forward", _v(feat), ld, C_, _v(label), _v(aff), _v(ws), _v(out7), N, h, w, radius, dtype_code(feat) if dtype is None else dtype)
+def aff_loss_backward(feat, ld, C_, label, aff, out7, gscale, d_feat, ld_d, N, h, w, radius, dtype=None):
+    _call("wseg_aff_loss_backward", _v(feat), ld, C_, _v(label), _v(aff), _v(out7), _v(gscale), _v(d_feat), ld_d, N, h, w, radius,
+          dtype_code(feat) if dtype is None else dtype)
+
 # ---------------------------------------------------------------------------------------------- dense CRF, exact mean field (csrc/crf.hip)
 CRF_PIX_ALIGN, CRF_MAX_LABELS, CRF_MAX_COLUMNS = 128, 32, 64     # WSEG_CRF_*
 CRF_BG_CONST, CRF_BG_POWER = 0, 1

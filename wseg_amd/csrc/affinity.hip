@@ -10,35 +10,9 @@
 //   random_walk   2^logt stencil applications per CAM plane, one workgroup per plane, the plane ping-ponged in LDS
 //   rw_pool       bg plane + class planes + zero padding + 8x8 average pooling
 //   rw_finish     bilinear upsample (align_corners=False) + arg-max + crop, written as uint8
-#include "common.h"
+#include "aff_geo.h"
 
 namespace {
-
-struct AffGeo {
-  int P, h, w, r, cw, n_from;
-  int dy[WSEG_AFF_MAX_OFFSETS], dx[WSEG_AFF_MAX_OFFSETS];
-};
-
-// the reference's offset order (tool/pyutils.py get_indices_of_pairs)
-int aff_offsets(int r, int* dy, int* dx) {
-  if (r < 2 || r > 6) return -1;
-  int n = 0;
-  for (int x = 1; x < r; ++x) { if (dy) { dy[n] = 0; dx[n] = x; } ++n; }
-  for (int y = 1; y < r; ++y)
-    for (int x = -r + 1; x < r; ++x)
-      if (x * x + y * y < r * r) { if (dy) { dy[n] = y; dx[n] = x; } ++n; }
-  return n;
-}
-
-int aff_geo(int h, int w, int r, AffGeo& g) {
-  WSEG_CHECK(r >= 2 && r <= 6, "aff: radius %d outside [2, 6] (the reference's pair set is empty below 2)", r);
-  WSEG_CHECK(h >= r && w >= 2 * r - 1, "aff: a %dx%d map has no 'from' pixel at radius %d", h, w, r);
-  g.P = aff_offsets(r, g.dy, g.dx);
-  g.h = h; g.w = w; g.r = r;
-  g.cw = w - 2 * (r - 1);
-  g.n_from = (h - r + 1) * g.cw;
-  return 0;
-}
 
 // one wave per (image, from pixel): the from row stays in registers (8 channels per lane), every to row is one coalesced load
 template <int DT>

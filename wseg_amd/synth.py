@@ -161,3 +161,16 @@ def synthetic_rgb_image(H, W, seed=0):
         img[inside] = r[5 * k + 2:5 * k + 5] * 255
     img += (20 * xx / W).unsqueeze(-1) + 24 * (u - 0.5)
     return img.round().clamp_(0, 255).to(torch.uint8)
+
+
+def synthetic_aff_label_map(h, w, seed=0, classes=(3, 11), block=3, p_bg=0.35, p_ignore=0.15):
+    """uint8 [h, w] AffinityNet label map (0 background, a class number, 255 ignore) in block x block patches, so that pairs of all three
+    kinds (background, foreground, negative) and ignored pixels occur at every radius."""
+    bh, bw = -(-h // block), -(-w // block)
+    u = _uniform("afflab", seed, (bh, bw), 0.0, 1.0)
+    p_cls = (1.0 - p_bg - p_ignore) / len(classes)
+    coarse = torch.full((bh, bw), 255, dtype=torch.uint8)
+    coarse[u < p_bg] = 0
+    for i, c in enumerate(classes):
+        coarse[(u >= p_bg + i * p_cls) & (u < p_bg + (i + 1) * p_cls)] = c
+    return coarse.repeat_interleave(block, 0).repeat_interleave(block, 1)[:h, :w].contiguous()
