@@ -398,6 +398,17 @@ int wseg_aff_loss_forward(const void* feat, int ld, int C, const unsigned char* 
 int wseg_aff_loss_backward(const void* feat, int ld, int C, const unsigned char* label, const float* aff, const float* out7,
                            const float* gscale, float* d_feat, int ld_d, int N, int h, int w, int radius, int dtype, void* stream);
 
+/* ---- AffinityNet head, training (network/resnet38_aff.py:39-42: f8_3, f8_4, f8_5, f9 = F.elu(conv(.))): the ELU backward on pixel rows ----
+ *   dz[m][c] = gscale * g[m][c] * (y[m][c] > 0 ? 1 : y[m][c] + 1)   for m in [0, M), c in [0, C)
+ * y: the saved ELU OUTPUT (elu' = 1 above zero, exp(z) = y + 1 below: no pre-activation is kept); g: the upstream gradient; gscale: one f32
+ * on the device, NULL = 1 (nothing synchronises with the host).  g, y, dz: rows of ld_g / ld_y / ld_dz elements in g_dtype / y_dtype /
+ * dz_dtype (WSEG_F32 or WSEG_BF16 each, in any combination: the kernel is also the f32 -> bf16 cast of the loss gradient).  Streaming:
+ * 16-byte loads and stores, so C % 8 == 0, every ld % 8 == 0 and >= C, 16-byte aligned bases — anything else is refused before any
+ * device call.  Columns >= C of dz are never written.  dz may alias g when dtype and ld agree.
+ * Exact: y > 0 gives gscale * g rounded once to dz_dtype; y == -1 gives 0; y == 0 takes the y + 1 branch (derivative 1). */
+int wseg_elu_backward_rows(const void* g, int ld_g, int g_dtype, const void* y, int ld_y, int y_dtype, const float* gscale, void* dz,
+                           int ld_dz, int dz_dtype, long M, int C, void* stream);
+
 /* ---- fully connected CRF, mean field with exact Gaussian kernels (contrast_infer.py:102-134 --out_crf, aff_prepare.py:34-50) ----------
  * The reference calls pydensecrf, whose filters are a permutohedral-lattice approximation; these entry points evaluate every pair
  * (DESIGN.md §3 "crf" states the update).  One image of N = H*W pixels (pixel i = y*W + x), M labels, S label sets sharing the image.

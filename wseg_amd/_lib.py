@@ -452,6 +452,17 @@ def aff_loss_backward(feat, ld, C_, label, aff, out7, gscale, d_feat, ld_d, N, h
     _call("wseg_aff_loss_backward", _v(feat), ld, C_, _v(label), _v(aff), _v(out7), _v(gscale), _v(d_feat), ld_d, N, h, w, radius,
           dtype_code(feat) if dtype is None else dtype)
 
+
+# ---------------------------------------------------------------------------------------------- AffinityNet head, training (csrc/aff_head.hip)
+def elu_backward_rows(g, ld_g, y, ld_y, gscale, dz, ld_dz, M, C_):
+    """dz[m, c] = gscale * g[m, c] * (y[m, c] > 0 ? 1 : y[m, c] + 1) for c < C_ on M pixel rows; y: the saved ELU output; gscale: a one-element
+    f32 device tensor or None; g / y / dz: f32 or bf16 tensors, each of its own ld (dz may be g itself)."""
+    for name, t_, ld in (("g", g, ld_g), ("y", y, ld_y), ("dz", dz, ld_dz)):
+        if t_.numel() < (M - 1) * ld + C_:       # (raw pointers beyond this line)
+            raise RuntimeError(f"elu_backward_rows: {name} has {t_.numel()} elements, {M} rows of ld {ld} with {C_} columns need {(M - 1) * ld + C_}")
+    _call("wseg_elu_backward_rows", _v(g), ld_g, dtype_code(g), _v(y), ld_y, dtype_code(y), _v(gscale), _v(dz), ld_dz, dtype_code(dz), C.c_long(M), C_)
+
+
 # ---------------------------------------------------------------------------------------------- dense CRF, exact mean field (csrc/crf.hip)
 CRF_PIX_ALIGN, CRF_MAX_LABELS, CRF_MAX_COLUMNS = 128, 32, 64     # WSEG_CRF_*
 CRF_BG_CONST, CRF_BG_POWER = 0, 1

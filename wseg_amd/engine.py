@@ -20,6 +20,8 @@ from . import _lib as L
 
 HEAD_LD = 192          # fused head rows: [f_proj 128 | cam 21 | zero pad 43]  (a 256-wide row for the 256-tile kernels measured slower: profiles/HISTORY.md)
 FEAT_LD = 256          # PCM feature rows: [f8_3 64 | f8_4 128 | x_s 3 | zero pad 61]
+AFF_FEAT_C = 448       # AffinityNet feature rows [f8_3 64 | f8_4 128 | f8_5 256]: the concat of network/resnet38_aff.py:47 is three column slices
+AFF_FEAT_SLICES = {"f8_3": (0, 64), "f8_4": (64, 192), "f8_5": (192, 448)}
 
 
 CONTRAST_FLAT_HEAD_ORDER = ("fc_proj", "fc8", "f8_3", "f8_4", "f9")
@@ -665,6 +667,48 @@ class Engine:
         st = self._run_blocks(xs, None, 0, len(arch.BLOCKS), False, None)
         self._join_late_packs(xs[0].device)
         return st, _Pass(st["N"], xs[0].device, st["dt"], self.packs)
+
+    def run_aff_head(self, conv4, conv5, t, dims, N, ps=None):
+        """The AffinityNet head as a unit (network/resnet38_aff.py:39-42): the three 1x1 ELU convs of conv4 / conv5 / t = relu(bn7(conv6)) into the
+        column slices [0,64) / [64,192) / [192,448) of `feat`, then f9 + ELU.  Inputs are pixel rows in the mode's dtype; returns (feat [M,448],
+        f9 [M,448]).  ps: the pass run_backbone returned (inference); None: a pass on the current packs."""
+        if ps is None:
+            dev = t.device
+            P = self.ensure_packs(dev, DT_OF[self.net.precision])
+            self._join_late_packs(dev)
+            ps = _Pass(N, dev, DT_OF[self.net.precision], P)
+        M = ps.rows_of(dims)
+        C = AFF_FEAT_C
+
+        def conv(inp, name, out, cin, cout):                  # 1x1 conv + ELU into a column slice of `out`
+            ps.conv(Conv(name, cin, cout, 1, 1, 1, dims, dims), inp, out, epi=3, ld_out=C)
+
+        feat = ps.E(M, C)
+        for name, inp in (("f8_3", conv4), ("f8_4", conv5), ("f8_5", t)):
+            (cout, cin), c0 = arch.AFF_HEAD_CONVS[name], AFF_FEAT_SLICES[name][0]
+            conv(inp, name, feat.view(-1)[c0:] if c0 else feat, cin, cout)
+        f9 = ps.E(M, C)
+        conv(feat, "f9", f9, C, C)
+        return feat, f9
+
+    def aff_head_wt(self, device):
+        """P["wt"] of the four AffinityNet head convs, the data-gradient packs [IC][1][OC] in the mode's dtype (split-bf16: pre-split), made from the f32
+        masters on first use per set of packs: inference never pays for them.  Returns the current packs."""
+        dt = DT_OF[self.net.precision]
+        with self.lock:
+            P = self._ensure_packs(device, dt)
+            if "f9" not in P["wt"]:
+                pdt = L.F32 if dt == L.F32X3 else dt
+                for nm, off, n, (ci, _t, co) in self.aff_head_wt_specs():
+                    wt = torch.empty(ci, 1, co, device=device, dtype=L.TORCH_DTYPE[dt])
+                    L.pack_weights(self.flat_w[off:off + n], None, wt, co, 1, ci, co, ci, pdt)
+                    P["wt"][nm] = self._x3(wt) if dt == L.F32X3 else wt
+        self._join_late_packs(device)
+        return P
+
+    def aff_head_wt_specs(self):
+        """[(name, offset of its f32 master [OC][1][IC] in the flat buffers, numel, shape [IC][1][OC] of its transposed pack)] of the AffinityNet head"""
+        return [(nm, *self.offsets[nm], (ci, 1, co)) for nm, (co, ci) in self.net.HEAD_CONVS.items()]
 
     def run_forward(self, xs, save, lowres=False, prefix=None):
         """xs: list of one or two image batches (same N).  Two views are BATCHED: every activation is one row

@@ -4,8 +4,10 @@ Mirrors the public contract of network/resnet38_aff.py (+ network/resnet38d.py:1
 returning the pair affinities [N, P, n_from] (or, with to_dense, the dense [area, area] matrix of one image as a device tensor),
 `.normalize`, `.get_parameter_groups()`, and the reference's state_dict keys (the backbone, then f8_3, f8_4, f8_5, f9).  The
 sub-modules are parameter containers: the backbone runs through wseg_amd.engine (the contrast net's kernels and packs), the
-ELU head on the implicit-GEMM conv (epilogue 3), the pairs / dense scatter in csrc/affinity.hip.  Training (aff_train.py) is out
-of scope: a forward in training mode raises.
+ELU head on the implicit-GEMM conv (epilogue 3; Engine.run_aff_head), the pairs / dense scatter in csrc/affinity.hip.  Of training
+(aff_train.py) the head exists on its own — wseg_amd/aff_head.py: its training-mode forward and its backward down to conv4 / conv5 /
+conv6, fed by wseg_amd/aff_loss.py — but the backbone cannot take those gradients yet, so a forward of the whole
+net in training mode still raises.
 """
 import os
 
@@ -18,7 +20,7 @@ from . import engine
 from . import _lib as L
 from .resnet38_contrast import Net as _ContrastNet, Normalize, _Block
 
-FEAT_C = 448                                    # [f8_3 64 | f8_4 128 | f8_5 256]: the concat of resnet38_aff.py:47 is three column slices
+FEAT_C = engine.AFF_FEAT_C                      # [f8_3 64 | f8_4 128 | f8_5 256]: the concat of resnet38_aff.py:47 is three column slices
 DEFAULT_RADIUS = 5
 PREDEFINED_FEATURESIZE = 448 // 8               # resnet38_aff.py:27-29 (the same pair set as the general rule at 56 x 56)
 
@@ -105,22 +107,13 @@ class Net(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("wseg_amd.resnet38_aff runs only on an MI355X (HIP) device; there is no CPU fallback")
         x = x.contiguous().float()
-        st, ps = self._engine.active(x.device).run_backbone([x])       # conv4 / conv5 / conv6 (resnet38d.py:160-189)
+        eng = self._engine.active(x.device)
+        st, ps = eng.run_backbone([x])                                 # conv4 / conv5 / conv6 (resnet38d.py:160-189)
         N = x.shape[0]
         dims = st["dims"]
         (h, w), = dims
         r = pair_radius(h, w, self.radius)
-        M = N * h * w
-
-        def conv(inp, name, out, cin, cout):                  # 1x1 conv + ELU into a column slice of `out`
-            ps.conv(engine.Conv(name, cin, cout, 1, 1, 1, dims, dims), inp, out, epi=3, ld_out=FEAT_C)
-
-        feat = ps.E(M, FEAT_C)
-        conv(st["conv4"], "f8_3", feat, 512, 64)
-        conv(st["conv5"], "f8_4", feat.view(-1)[64:], 1024, 128)
-        conv(st["t"], "f8_5", feat.view(-1)[192:], 4096, 256)
-        f9 = ps.E(M, FEAT_C)
-        conv(feat, "f9", f9, FEAT_C, FEAT_C)
+        _, f9 = eng.run_aff_head(st["conv4"], st["conv5"], st["t"], dims, N, ps=ps)
         n_from = (h - r + 1) * (w - 2 * r + 2)
         aff = torch.empty(N, L.aff_num_offsets(r), n_from, device=x.device, dtype=torch.float32)
         L.aff_pairs(f9, FEAT_C, FEAT_C, aff, N, h, w, r)
