@@ -168,7 +168,10 @@ __global__ __launch_bounds__(256) void rw_finish_kernel(const float* __restrict_
   int arg = 0;
   for (int c = 0; c < planes; ++c) {
     const float* p = cam + c * per;
-    const float v = hy * (hx * p[y0 * dw + x0] + lx * p[y0 * dw + x1]) + ly * (hx * p[y1 * dw + x0] + lx * p[y1 * dw + x1]);
+    // explicit fmas: left to the compiler's contraction, the peeled plane 0 and the loop body were fused differently, so a plane >= 1
+    // that is a bitwise copy of plane 0 could come out one ulp higher and win the tie that belongs to the lower index
+    const float top = fmaf(lx, p[y0 * dw + x1], hx * p[y0 * dw + x0]), bot = fmaf(lx, p[y1 * dw + x1], hx * p[y1 * dw + x0]);
+    const float v = fmaf(ly, bot, hy * top);
     if (c == 0 || v > best) { best = v; arg = c; }
   }
   pred[t] = (unsigned char)arg;
