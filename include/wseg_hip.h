@@ -338,6 +338,34 @@ size_t wseg_sizeof_aug_desc(void);
 int wseg_augment_batch(const wseg_aug_desc* descs_dev, int n, int max_pixels /* largest H*rw or rh*rw of the batch */, const float* lut /* [3][256] */,
                        int crop, unsigned long long* lum_sums /* scratch [n][4] */, void* stream);
 
+/* ---- AffinityNet training data on the device (aff_train.py:39-60 in the zip order of voc12/data.py:237-249): ColorJitter -> joint
+ * RandomCrop of the image and the 42 CRF score planes into a crop x crop container -> normalise -> joint horizontal flip OF THE CONTAINER
+ * (x -> crop-1-x) -> CHW image / 8x8 block means of the scores -> label map (voc12/data.py:251-258).  No resize.
+ *
+ * Image: the descriptors are wseg_aug_desc with rw = W, rh = H and `img` = the uploaded decoded image itself (the colour ops run on it in
+ * place: it is scratch); src, tmp and the coefficient tables are not read.  `lut` is the table of FLOAT32 arithmetic
+ * ((float(v) / 255.f - mean) / std, as numpy evaluates normalize on the float32 container); container pixels outside the pasted rectangle
+ * get lut[c][0] = normalize(0), not 0. */
+int wseg_aff_augment_batch(const wseg_aug_desc* descs_dev, int n, int max_pixels /* largest H*W of the batch */, const float* lut /* [3][256] */,
+                           int crop, unsigned long long* lum_sums /* scratch [n][4] */, void* stream);
+/* Labels: per stack (0 low alpha, 1 high alpha) only the planes with a non-zero value are shipped, np of them in ascending plane id; an
+ * absent plane is a zero plane.  Scores are >= 0.  Plane k of stack s is planes[s] + k * plane_stride, [H][W] f32 (4-byte aligned rows).
+ * Per output cell: the mean over the 8x8 container window of every shipped plane (zeros outside the pasted rectangle, always / 64), the
+ * arg-max per stack (start: value 0 at plane 0; a later plane wins only when strictly greater = np.argmax over the dense 21 planes), then
+ *   label = arg_lo;  arg_lo == 0 -> 255;  arg_hi == 0 -> 0;  max of all means < 1e-5f -> 255.
+ * One launch for the batch, no atomics, a fixed summation order: out_u8 [n][crop/8][crop/8] is bit-identical from run to run. */
+typedef struct {
+  const float* planes[2];
+  const int32_t* ids[2];                              /* [np] plane ids, ascending, each in [0, 21) */
+  int32_t np[2];                                      /* 0..21 */
+  int32_t H, W;
+  int64_t plane_stride;                               /* floats between two shipped planes of a stack (>= H*W) */
+  int32_t flip;
+  int32_t cont_top, cont_left, img_top, img_left, ch, cw;   /* RandomCrop, as in wseg_aug_desc */
+} wseg_aff_label_desc;
+size_t wseg_sizeof_aff_label_desc(void);
+int wseg_aff_labels_batch(const wseg_aff_label_desc* descs_dev, int n, int crop /* % 8 == 0 */, unsigned char* out_u8, void* stream);
+
 /* ---- fused SGD step (tool/torchutils.py:23-33 -> torch.optim.SGD.step) ------------------------
  * One pass over the flat buffers: d = g*grad_scale + wd*p; buf = first ? d : momentum*buf + d;
  * p -= lr*buf.  Segments [begin,end) carry the per-group lr / weight_decay (contrast_train.py:91-96).

@@ -453,6 +453,30 @@ def aff_loss_backward(feat, ld, C_, label, aff, out7, gscale, d_feat, ld_d, N, h
           dtype_code(feat) if dtype is None else dtype)
 
 
+# ---------------------------------------------------------------------------------------------- AffinityNet training data (csrc/aff_data.hip, csrc/augment.hip)
+class AffLabelDesc(C.Structure):                 # wseg_aff_label_desc
+    _fields_ = [("planes", C.c_void_p * 2), ("ids", C.c_void_p * 2), ("np", C.c_int32 * 2), ("H", C.c_int32), ("W", C.c_int32),
+                ("plane_stride", C.c_int64), ("flip", C.c_int32), ("cont_top", C.c_int32), ("cont_left", C.c_int32), ("img_top", C.c_int32),
+                ("img_left", C.c_int32), ("ch", C.c_int32), ("cw", C.c_int32)]
+
+
+lib.wseg_sizeof_aff_label_desc.restype = C.c_size_t
+if lib.wseg_sizeof_aff_label_desc() != C.sizeof(AffLabelDesc):
+    raise ImportError(f"wseg_aff_label_desc: library {lib.wseg_sizeof_aff_label_desc()} bytes, binding {C.sizeof(AffLabelDesc)}: rebuild libwseg_hip.so")
+
+
+def aff_augment_batch(descs_dev, n, max_pixels, lut, crop, lum_sums):
+    """descs_dev: address of n wseg_aug_desc on the device (rw = W, rh = H, img = the uploaded image, jittered in place)."""
+    _call("wseg_aff_augment_batch", _v(descs_dev), n, max_pixels, _v(lut), crop, _v(lum_sums))
+
+
+def aff_labels_batch(descs_dev, n, crop, out_u8):
+    """descs_dev: address of n wseg_aff_label_desc on the device; out_u8: uint8 [n, crop/8, crop/8]."""
+    if out_u8.dtype != torch.uint8 or not out_u8.is_contiguous() or out_u8.numel() != n * (crop // 8) ** 2:       # (raw pointers beyond this line)
+        raise RuntimeError(f"aff_labels_batch: out_u8 must be a contiguous uint8 tensor of {n} x {crop // 8} x {crop // 8}")
+    _call("wseg_aff_labels_batch", _v(descs_dev), n, crop, _v(out_u8))
+
+
 # ---------------------------------------------------------------------------------------------- AffinityNet head, training (csrc/aff_head.hip)
 def elu_backward_rows(g, ld_g, y, ld_y, gscale, dz, ld_dz, M, C_):
     """dz[m, c] = gscale * g[m, c] * (y[m, c] > 0 ? 1 : y[m, c] + 1) for c < C_ on M pixel rows; y: the saved ELU output; gscale: a one-element

@@ -181,3 +181,40 @@ extern "C" int wseg_augment_batch(const wseg_aug_desc* descs_dev, int n, int max
   WSEG_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- the image side of AffinityNet training data (aff_train.py:39-60): ColorJitter -> RandomCrop -> normalize -> flip -> CHW.  No resize:
+// the colour ops above run with rw = W, rh = H on the uploaded image in place.  What differs from aug_finish_kernel: the flip acts on the
+// crop x crop CONTAINER (after the crop), the table is the float32-arithmetic one, and the padding is normalize(0) = lut[c][0], not 0.
+namespace {
+
+__global__ void aff_finish_kernel(const wseg_aug_desc* __restrict__ descs, const float* __restrict__ lut, int crop) {
+  const wseg_aug_desc d = descs[blockIdx.y];
+  const long total = (long)crop * crop;
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    const int y = (int)(idx / crop), x = (int)(idx - (long)y * crop);
+    const int cy = y - d.cont_top, cx = (d.flip ? crop - 1 - x : x) - d.cont_left;
+    float v0 = lut[0], v1 = lut[256], v2 = lut[512];
+    if (cy >= 0 && cy < d.ch && cx >= 0 && cx < d.cw) {
+      const unsigned char* p = d.img + ((long)(cy + d.img_top) * d.rw + (cx + d.img_left)) * 3;
+      v0 = lut[p[0]]; v1 = lut[256 + p[1]]; v2 = lut[512 + p[2]];
+    }
+    d.out[idx] = v0; d.out[total + idx] = v1; d.out[2 * total + idx] = v2;
+  }
+}
+
+}  // namespace
+
+extern "C" int wseg_aff_augment_batch(const wseg_aug_desc* descs_dev, int n, int max_pixels, const float* lut, int crop,
+                                      unsigned long long* lum_sums, void* stream) {
+  WSEG_CHECK(descs_dev && n > 0 && n <= 65535 && max_pixels > 0 && lut && crop > 0 && lum_sums, "aff_augment_batch: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)std::min(1024, (max_pixels + 255) / 256), n), blk(256);
+  (void)hipMemsetAsync(lum_sums, 0, sizeof(unsigned long long) * 4 * n, s);
+  for (int stage = 0; stage < 4; ++stage) {
+    hipLaunchKernelGGL(aug_lum_sum_kernel, grid, blk, 0, s, descs_dev, stage, lum_sums);
+    hipLaunchKernelGGL(aug_color_kernel, grid, blk, 0, s, descs_dev, stage, (const unsigned long long*)lum_sums);
+  }
+  hipLaunchKernelGGL(aff_finish_kernel, dim3((unsigned)((crop * crop + 255) / 256), n), blk, 0, s, descs_dev, lut, crop);
+  WSEG_LAUNCH_CHECK();
+  return 0;
+}

@@ -175,3 +175,78 @@ def train_transform(model, crop_size):
     """contrast_train.py:64-75."""
     return [RandomResizeLong(448, 768), RandomHorizontalFlip(), ColorJitter(0.3, 0.3, 0.3, 0.1), np.asarray,
             model.normalize, RandomCrop(crop_size), HWC_to_CHW, torch.from_numpy]
+
+
+# ---------------------------------------------------------------------------------------------- AffinityNet training data (aff_train.py:39-60)
+class RandomHorizontalFlipArray:                           # tool/imutils.py:141-157: one random BIT, np.fliplr on the HWC array
+    def __call__(self, arr):
+        return np.fliplr(arr).copy() if bool(random.getrandbits(1)) else arr
+
+
+class AvgPool2d:
+    """tool/imutils.py:130-138 (skimage.measure.block_reduce with np.mean) for an [h, w, c] array whose sides are multiples of ksize, which
+    is all the AffinityNet chain feeds it: block means in the array's own dtype (float32 in, float32 out)."""
+
+    def __init__(self, ksize):
+        self.ksize = ksize
+
+    def __call__(self, arr):
+        h, w, c = arr.shape
+        k = self.ksize
+        if h % k or w % k:
+            raise ValueError(f"AvgPool2d({k}): sides {h} x {w} are no multiples of {k}")
+        return arr.reshape(h // k, k, w // k, k, c).mean(axis=(1, 3))
+
+
+def aff_train_transform(model, crop_size):
+    """aff_train.py:39-60: the (joint, image, label) transform lists VOC12AffDataset applies in zip order — ColorJitter on the PIL image,
+    np.asarray, joint RandomCrop THEN normalize (on the float32 container: numpy float32 arithmetic, padding = normalize(0)), joint flip
+    THEN HWC_to_CHW / AvgPool2d(8).  There is no RandomResizeLong in this chain."""
+    if crop_size % 8:
+        raise ValueError(f"aff_train_transform: crop {crop_size} is no multiple of 8")
+    joint = [None, None, RandomCrop(crop_size), RandomHorizontalFlipArray()]
+    img = [ColorJitter(0.3, 0.3, 0.3, 0.1), np.asarray, model.normalize, HWC_to_CHW]
+    label = [None, None, None, AvgPool2d(8)]
+    return joint, img, label
+
+
+def aff_apply_transforms(img, la_scores, ha_scores, transforms):
+    """voc12/data.py:233-258 for one decoded sample: img a PIL RGB image, la_scores / ha_scores float32 [21, H, W] (the files aff_prepare
+    writes), transforms = aff_train_transform(...) -> (img float32 [3, crop, crop], label uint8 [crop/8, crop/8]: 0 background, 1..20 a
+    class, 255 ignore).  The reference goes on to its three pair-label tensors; here the map is the contract (aff_loss.pair_labels gives
+    the three tensors to whoever wants them)."""
+    label = np.array(list(la_scores) + list(ha_scores))
+    label = np.transpose(label, (1, 2, 0))
+    for joint_t, img_t, label_t in zip(*transforms):
+        if joint_t:
+            img_label = joint_t(np.concatenate((img, label), axis=-1))      # (uint8 with float32: a float32 array)
+            img, label = img_label[..., :3], img_label[..., 3:]
+        if img_t:
+            img = img_t(img)
+        if label_t:
+            label = label_t(label)
+    no_score_region = np.max(label, -1) < np.float32(1e-5)                   # (the comparison is on the float32 means)
+    label_la, label_ha = np.array_split(label, 2, axis=-1)
+    label_la = np.argmax(label_la, axis=-1).astype(np.uint8)
+    label_ha = np.argmax(label_ha, axis=-1).astype(np.uint8)
+    label = label_la.copy()
+    label[label_la == 0] = 255
+    label[label_ha == 0] = 0
+    label[no_score_region] = 255
+    return np.ascontiguousarray(img), label
+
+
+class VOC12AffDataset(VOC12ImageDataset):                  # voc12/data.py:201-261
+    """(img float32 [3, crop, crop], label uint8 [crop/8, crop/8]) per image, on the host (numpy / PIL): the CPU path of AffinityNet
+    training data and the yardstick of the device path (wseg_amd/aff_data.py).  Score files: `<la_crf_dir>/<name>.npy` and
+    `<ha_crf_dir>/<name>.npy`, float32 [21, H, W] each."""
+
+    def __init__(self, img_name_list_path, label_la_dir, label_ha_dir, voc12_root, transforms):
+        super().__init__(img_name_list_path, voc12_root, transform=None)
+        self.label_la_dir, self.label_ha_dir, self.transforms = label_la_dir, label_ha_dir, transforms
+
+    def __getitem__(self, idx):
+        name, img = super().__getitem__(idx)
+        la = np.load(os.path.join(self.label_la_dir, name + '.npy'))
+        ha = np.load(os.path.join(self.label_ha_dir, name + '.npy'))
+        return aff_apply_transforms(img, la, ha, self.transforms)
