@@ -425,6 +425,12 @@ int wseg_aff_loss_forward(const void* feat, int ld, int C, const unsigned char* 
  * no valid pair), columns >= C are untouched; a channel on which the two rows of a pair tie gets no contribution (sign(0) = 0). */
 int wseg_aff_loss_backward(const void* feat, int ld, int C, const unsigned char* label, const float* aff, const float* out7,
                            const float* gscale, float* d_feat, int ld_d, int N, int h, int w, int radius, int dtype, void* stream);
+/* The backward of wseg_aff_pairs: d_feat[N*h*w][ld_d] f32 = sum over the pairs a pixel belongs to of d_aff[n][p][f] * d aff[n][p][f] / d feat,
+ * with aff = exp(-mean_c |f_to - f_from|) as wseg_aff_pairs wrote it (read, not recomputed) and feat the rows it read.  The row walk of
+ * wseg_aff_loss_backward with another coefficient (-aff * d_aff / C * sign(f_to - f_from), sign(0) = 0): same write contract, no atomics,
+ * bit-identical from run to run; rows of pixels in no pair are zero. */
+int wseg_aff_pairs_backward(const void* feat, int ld, int C, const float* aff, const float* d_aff, float* d_feat, int ld_d, int N,
+                            int h, int w, int radius, int dtype, void* stream);
 
 /* ---- AffinityNet head, training (network/resnet38_aff.py:39-42: f8_3, f8_4, f8_5, f9 = F.elu(conv(.))): the ELU backward on pixel rows ----
  *   dz[m][c] = gscale * g[m][c] * (y[m][c] > 0 ? 1 : y[m][c] + 1)   for m in [0, M), c in [0, C)

@@ -451,6 +451,15 @@ def aff_loss_forward(feat, ld, C_, label, aff, ws, out7, N, h, w, radius, dtype=
 def aff_loss_backward(feat, ld, C_, label, aff, out7, gscale, d_feat, ld_d, N, h, w, radius, dtype=None):
     _call("wseg_aff_loss_backward", _v(feat), ld, C_, _v(label), _v(aff), _v(out7), _v(gscale), _v(d_feat), ld_d, N, h, w, radius,
           dtype_code(feat) if dtype is None else dtype)
+def aff_pairs_backward(feat, ld, C_, aff, d_aff, d_feat, ld_d, N, h, w, radius, dtype=None):
+    """d_feat f32 [N*h*w][ld_d] from d_aff [N, P, n_from] f32 and the aff / feat of aff_pairs (the loss backward's row walk: every row written once)."""
+    M, npairs = N * h * w, N * aff_num_offsets(radius) * (h - radius + 1) * (w - 2 * radius + 2)
+    for name, t_, need in (("feat", feat, (M - 1) * ld + C_), ("aff", aff, npairs), ("d_aff", d_aff, npairs), ("d_feat", d_feat, (M - 1) * ld_d + C_)):
+        if t_.numel() < need:                    # (raw pointers beyond this line)
+            raise RuntimeError(f"aff_pairs_backward: {name} has {t_.numel()} elements, the launch touches {need}")
+    if aff.dtype != torch.float32 or d_aff.dtype != torch.float32 or d_feat.dtype != torch.float32 or not (aff.is_contiguous() and d_aff.is_contiguous()):
+        raise RuntimeError("aff_pairs_backward: aff, d_aff and d_feat must be float32, aff and d_aff contiguous")
+    _call("wseg_aff_pairs_backward", _v(feat), ld, C_, _v(aff), _v(d_aff), _v(d_feat), ld_d, N, h, w, radius, dtype_code(feat) if dtype is None else dtype)
 
 
 # ---------------------------------------------------------------------------------------------- AffinityNet training data (csrc/aff_data.hip, csrc/augment.hip)

@@ -18,7 +18,7 @@ Weight gradients ACCUMULATE into the engine's flat gradient buffer (Engine.grad_
 The f8_5 data gradient takes the optional BN-ReLU backward operands of the contrast head's data gradient (scale / mask / drop: epilogue
 1), so that the backbone's backward can later fold bn7's ReLU in; with none it is the plain gradient w.r.t. t = relu(bn7(conv6)).
 Every data gradient and its weight gradient are two launches (the joint grid of wseg_conv_bwd_pair is not used here).  Nothing
-synchronises with the host.  What of aff_train remains — the backbone's gradient taps, trainer, dataset, CLI — is DESIGN.md §8 item 8.
+synchronises with the host.  The rest of the step — the backbone's backward with gradient taps, trainer, CLI — is wseg_amd/aff_train.py.
 """
 import torch
 

@@ -11,8 +11,8 @@ three indicators of a pair follow from its two label bytes inside the kernels, a
 
 The seven scalars `loss, bg_loss, fg_loss, neg_loss, bg_cnt, fg_cnt, neg_cnt` (the keys of aff_train.py's AverageMeter, in its order) and
 the gradient are bit-identical from run to run: no kernel accumulates in an order that depends on scheduling.  Nothing synchronises with
-the host.  The ELU head under the loss is wseg_amd/aff_head.py (its output is consumed here without a copy); the rest of aff_train (the
-backbone's gradient taps, trainer, CLI) is not built: DESIGN.md §8; the label map comes from wseg_amd/aff_data.py on the device.
+the host.  The ELU head under the loss is wseg_amd/aff_head.py (its output is consumed here without a copy); the trainer and CLI are
+wseg_amd/aff_train.py; the label map comes from wseg_amd/aff_data.py on the device.
 """
 import numpy as np
 import torch

@@ -8,6 +8,7 @@
 //   aff_loss_finish    one workgroup adds the partials in a fixed order (sums in f64, counts as integers) -> out[7]
 //   aff_loss_backward  one wave per (image, pixel) in gather form: every pair the pixel belongs to (as "from" with its P partners, as "to" of
 //                      the from pixels q - offset) adds k * sign(.) to the pixel's row, in a fixed order (no atomics, no scatter)
+//   aff_pairs_backward the same row walk with the coefficient of a plain d_aff [N, P, n_from]: the backward of wseg_aff_pairs
 // Nothing here is accumulated in an order that depends on scheduling: out[7] and d_feat are bit-identical from run to run.
 #include "aff_geo.h"
 
@@ -125,11 +126,14 @@ __device__ __forceinline__ float pair_coef(int kind, float v, const float (&w)[3
 
 __device__ __forceinline__ float sign0(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }   // sign(0) = 0: torch's abs backward
 
-template <int DT>
-__global__ __launch_bounds__(256) void aff_loss_backward_kernel(const void* __restrict__ feat, int ld, int C, const unsigned char* __restrict__ label,
-                                                                const float* __restrict__ aff, const float* __restrict__ out7,
-                                                                const float* __restrict__ gscale, float* __restrict__ d_feat, int ld_d, int N,
-                                                                AffGeo g) {
+// The row walk of the two gather-form backward kernels: the wave of pixel q = (n, y, x) visits, offset by offset, the pair q forms as "from" with
+// q + offset and the pair it forms as "to" of the from pixel q - offset, and adds k * sign(f_to - f_from) to (to) / subtracts it from (from) its
+// row, in that fixed order; `coef` says whether a pair counts and supplies its k.  Every row is written once (zeros where q is in no pair).
+//   coef.live(pix)                         false: the pixel is in no pair that counts (its row is zero)
+//   coef(n, p, f, from, to, k) -> bool     the pair (offset p, from index f) of image n between the pixel rows `from` and `to`
+template <int DT, class Coef>
+__device__ __forceinline__ void aff_pair_row_walk(const void* __restrict__ feat, int ld, int C, float* __restrict__ d_feat, int ld_d, int N,
+                                                  const AffGeo& g, const Coef& coef) {
   const int lane = threadIdx.x & 63;
   const int area = g.h * g.w;
   const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -141,23 +145,17 @@ __global__ __launch_bounds__(256) void aff_loss_backward_kernel(const void* __re
   const int groups = C >> 3;
   const bool act = lane < groups;
   const int c0 = act ? lane * 8 : 0;
-  const float gs = gscale ? gscale[0] : 1.f;
-  const float w[3] = {gs / (4.f * out7[4]), gs / (4.f * out7[5]), gs / (2.f * out7[6])};
-  const float fc = (float)C;
-  const float* an = aff + (long)n * g.P * g.n_from;
-  const unsigned lq = label[base + q];
   const bool q_from = y < ch && x >= x_lo && x < x_hi;
   float a[8], acc[8];
   load8<DT>(feat, (size_t)(base + q) * ld + c0, a);
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-  if (lq != 255u) {                                               // an ignore pixel is in no valid pair
+  if (coef.live(base + q)) {
     for (int p = 0; p < g.P; ++p) {
+      float k;
       if (q_from) {                                               // q = from, partner q + offset: d f_from -= k * sign(f_to - f_from)
         const long to = base + (long)(y + g.dy[p]) * g.w + x + g.dx[p];
-        const int kind = pair_kind(lq, label[to]);
-        if (kind >= 0) {                                          // (wave-uniform)
-          const float k = pair_coef(kind, an[(long)p * g.n_from + y * g.cw + (x - x_lo)], w, fc);
+        if (coef(n, p, y * g.cw + (x - x_lo), base + q, to, k)) { // (wave-uniform)
           float b[8];
           load8<DT>(feat, (size_t)to * ld + c0, b);
 #pragma unroll
@@ -167,9 +165,7 @@ __global__ __launch_bounds__(256) void aff_loss_backward_kernel(const void* __re
       const int iy = y - g.dy[p], ix = x - g.dx[p];
       if (iy >= 0 && iy < ch && ix >= x_lo && ix < x_hi) {        // q = to of the from pixel q - offset: d f_to += k * sign(f_to - f_from)
         const long from = base + (long)iy * g.w + ix;
-        const int kind = pair_kind(label[from], lq);
-        if (kind >= 0) {
-          const float k = pair_coef(kind, an[(long)p * g.n_from + iy * g.cw + (ix - x_lo)], w, fc);
+        if (coef(n, p, iy * g.cw + (ix - x_lo), from, base + q, k)) {
           float b[8];
           load8<DT>(feat, (size_t)from * ld + c0, b);
 #pragma unroll
@@ -179,6 +175,53 @@ __global__ __launch_bounds__(256) void aff_loss_backward_kernel(const void* __re
     }
   }
   if (act) store8<WSEG_F32>(d_feat, (size_t)(base + q) * ld_d + c0, acc);
+}
+
+// the loss's coefficient: the pair's kind from its two label bytes, dL / d aff from the seven scalars (an ignore pixel is in no valid pair)
+struct AffLossCoef {
+  const unsigned char* label;
+  const float* aff;
+  float w[3], fc;
+  int P, n_from;
+  __device__ __forceinline__ bool live(long pix) const { return label[pix] != 255u; }
+  __device__ __forceinline__ bool operator()(int n, int p, int f, long from, long to, float& k) const {
+    const int kind = pair_kind(label[from], label[to]);
+    if (kind < 0) return false;
+    k = pair_coef(kind, aff[((long)n * P + p) * n_from + f], w, fc);
+    return true;
+  }
+};
+
+// the coefficient of aff_pairs' own backward: every pair counts, d aff / d s = -aff / C times the incoming d_aff
+struct AffPairsCoef {
+  const float* aff;
+  const float* d_aff;
+  float fc;
+  int P, n_from;
+  __device__ __forceinline__ bool live(long) const { return true; }
+  __device__ __forceinline__ bool operator()(int n, int p, int f, long, long, float& k) const {
+    const long i = ((long)n * P + p) * n_from + f;
+    k = d_aff[i] * (-aff[i] / fc);
+    return true;
+  }
+};
+
+template <int DT>
+__global__ __launch_bounds__(256) void aff_loss_backward_kernel(const void* __restrict__ feat, int ld, int C, const unsigned char* __restrict__ label,
+                                                                const float* __restrict__ aff, const float* __restrict__ out7,
+                                                                const float* __restrict__ gscale, float* __restrict__ d_feat, int ld_d, int N,
+                                                                AffGeo g) {
+  const float gs = gscale ? gscale[0] : 1.f;
+  const AffLossCoef coef = {label, aff, {gs / (4.f * out7[4]), gs / (4.f * out7[5]), gs / (2.f * out7[6])}, (float)C, g.P, g.n_from};
+  aff_pair_row_walk<DT>(feat, ld, C, d_feat, ld_d, N, g, coef);
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void aff_pairs_backward_kernel(const void* __restrict__ feat, int ld, int C, const float* __restrict__ aff,
+                                                                 const float* __restrict__ d_aff, float* __restrict__ d_feat, int ld_d, int N,
+                                                                 AffGeo g) {
+  const AffPairsCoef coef = {aff, d_aff, (float)C, g.P, g.n_from};
+  aff_pair_row_walk<DT>(feat, ld, C, d_feat, ld_d, N, g, coef);
 }
 
 int aff_loss_check(const char* what, int ld, int C, int N, int dtype) {
@@ -230,6 +273,24 @@ extern "C" int wseg_aff_loss_backward(const void* feat, int ld, int C, const uns
     hipLaunchKernelGGL(aff_loss_backward_kernel<WSEG_BF16>, dim3((unsigned)blocks), dim3(256), 0, s, feat, ld, C, label, aff, out7, gscale, d_feat, ld_d, N, g);
   else
     hipLaunchKernelGGL(aff_loss_backward_kernel<WSEG_F32>, dim3((unsigned)blocks), dim3(256), 0, s, feat, ld, C, label, aff, out7, gscale, d_feat, ld_d, N, g);
+  WSEG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int wseg_aff_pairs_backward(const void* feat, int ld, int C, const float* aff, const float* d_aff, float* d_feat, int ld_d, int N,
+                                       int h, int w, int radius, int dtype, void* stream) {
+  AffGeo g;
+  if (int rc = aff_geo(h, w, radius, g)) return rc;
+  if (int rc = aff_loss_check("aff_pairs_backward", ld, C, N, dtype)) return rc;
+  WSEG_CHECK(ld_d >= C && ld_d % 8 == 0, "aff_pairs_backward: C=%d ld_d=%d (ld_d >= C, ld_d %% 8 == 0)", C, ld_d);
+  WSEG_CHECK(feat && aff && d_aff && d_feat, "aff_pairs_backward: null pointer");
+  const long blocks = aff_loss_blocks((long)N * h * w);
+  WSEG_CHECK(blocks < (1L << 31), "aff_pairs_backward: batch too large");
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == WSEG_BF16)
+    hipLaunchKernelGGL(aff_pairs_backward_kernel<WSEG_BF16>, dim3((unsigned)blocks), dim3(256), 0, s, feat, ld, C, aff, d_aff, d_feat, ld_d, N, g);
+  else
+    hipLaunchKernelGGL(aff_pairs_backward_kernel<WSEG_F32>, dim3((unsigned)blocks), dim3(256), 0, s, feat, ld, C, aff, d_aff, d_feat, ld_d, N, g);
   WSEG_LAUNCH_CHECK();
   return 0;
 }

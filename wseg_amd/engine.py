@@ -518,9 +518,10 @@ class Engine:
     MASK_SPECS = (("b6.dropout_2b1", 512, 0.3), ("b6.dropout_2b2", 1024, 0.3),
                   ("b7.dropout_2b1", 1024, 0.5), ("b7.dropout_2b2", 2048, 0.5), ("dropout7", 4096, 0.5))
 
-    def _masks(self, n, views, device):
+    def _masks(self, n, views, device, specs=None):
         """Dropout2d scales [views*n, C] per dropout site (rows of view 1, then view 2): injected (parity tests) or drawn
-        on the device — one uniform draw + one kernel for all five sites."""
+        on the device — one uniform draw + one kernel for all five sites (specs: a prefix of MASK_SPECS; the AffinityNet has no dropout7)."""
+        specs = specs or self.MASK_SPECS
         net = self.net
         if not net.training:
             return None
@@ -531,12 +532,12 @@ class Engine:
                 per_view.append({k: v.to(device=device, dtype=torch.float32) for k, v in m.items()})
             return {k: torch.cat([m[k] for m in per_view], dim=0).contiguous() for k in per_view[0]}
         rows = views * n
-        total = sum(c for _, c, _ in self.MASK_SPECS)
+        total = sum(c for _, c, _ in specs)
         u = torch.rand(rows * total, device=device)
         flat = torch.empty_like(u)
         L.dropout_scale(u, flat, rows * (512 + 1024), 0.3, 0.5)          # the two b6 sites (p = 0.3) come first
         out, off = {}, 0
-        for key, c, _p in self.MASK_SPECS:
+        for key, c, _p in specs:
             out[key] = flat[off:off + rows * c].view(rows, c)
             off += rows * c
         return out
@@ -661,12 +662,55 @@ class Engine:
         prefix stream to the next step belongs to the caller's allocator pool (no record_stream bookkeeping: with it the reserved memory grew by 6 GB)."""
         return self._run_blocks(xs, None, 0, arch.N_FROZEN_BLOCKS, False, None, final_t=out)
 
-    def run_backbone(self, xs):
+    def run_backbone(self, xs, save=False):
         """conv1a and every block, no head (the AffinityNet puts its own on top).  Returns (state, pass): state["t"] = relu(bn7(conv6)),
-        state["conv4"] / ["conv5"] the inputs of b5 / b6, state["dims"] the stride-8 dims; `pass.conv` launches on the current packs."""
-        st = self._run_blocks(xs, None, 0, len(arch.BLOCKS), False, None)
-        self._join_late_packs(xs[0].device)
-        return st, _Pass(st["N"], xs[0].device, st["dt"], self.packs)
+        state["conv4"] / ["conv5"] the inputs of b5 / b6, state["dims"] the stride-8 dims; `pass.conv` launches on the current packs.
+        save: returns (state, pass, S) — S is the context run_trunk_backward takes: the trainable blocks' activations as run_forward
+        stores them, dims, N, dt and the four block masks (drawn in training mode, or injected; the AffinityNet has no dropout7: that site
+        is present as None), with S["fea"] = state["t"] (bn7's ReLU mask)."""
+        if not save:
+            st = self._run_blocks(xs, None, 0, len(arch.BLOCKS), False, None)
+            self._join_late_packs(xs[0].device)
+            return st, _Pass(st["N"], xs[0].device, st["dt"], self.packs)
+        assert len(xs) == 1, "the saved backbone pass takes one view"
+        dev, N = xs[0].device, xs[0].shape[0]
+        dt = DT_OF[self.net.precision]
+        self.ensure_packs(dev, dt)
+        masks = self._masks(N, 1, dev, self.MASK_SPECS[:4])
+        if masks is not None:
+            assert "dropout7" not in masks, "the AffinityNet backbone has four Dropout2d sites: injected masks carry no dropout7"
+            masks["dropout7"] = None
+        S = {"masks": masks, "dims": {}, "N": N, "V": 1, "dt": dt, "xs": xs}
+        prefix = self._run_blocks(xs, None, 0, arch.N_FROZEN_BLOCKS, False, None)      # (the frozen blocks keep nothing)
+        S["dims"].update(prefix["sdims"])
+        st = self._run_blocks(xs, prefix, arch.N_FROZEN_BLOCKS, len(arch.BLOCKS), True, S)
+        self._join_late_packs(dev)
+        ps = _Pass(N, dev, dt, self.packs)
+        S.update(fea=st["t"], hdims=st["dims"], M=ps.rows_of(st["dims"]), conv4=st["conv4"], conv5=st["conv5"])
+        return st, ps, S
+
+    def run_trunk_backward(self, S, D, taps=None):
+        """The backbone's backward on its own: the block loop of run_backward from D [M, 4096], the gradient at conv6 BEFORE bn7 (aff_head_backward's
+        d_t with scale = bn7's scale and mask = t), on the context S of run_backbone(save=True).  taps {"b5": d_conv4, "b6": d_conv5}: gradients
+        w.r.t. those blocks' input t = relu(bn_branch2a(x)) (pixel rows in the mode's dtype), added before the block's mask . scale.  Weight
+        gradients accumulate into flat_g, block_done fires as in run_backward; the PCM and contrast-head sections do not run."""
+        tdt = L.TORCH_DTYPE[S["dt"]]
+        taps = dict(taps or {})
+        blocks = {b[0]: b for b in arch.BLOCKS}
+        for nm, tap in list(taps.items()) + [("conv6", D)]:
+            if nm == "conv6":
+                rows, c = S["M"], 4096
+            else:
+                b = blocks.get(nm)
+                if b is None or nm in arch.FROZEN_BLOCKS or nm == "b3" or arch.block_same_shape(b):
+                    raise ValueError(f"run_trunk_backward: block {nm!r} takes no gradient tap (a trainable block with a skip conv, behind b3)")
+                rows, c = sum(S["N"] * h * w for (h, w) in S["dims"][nm][0]), b[2]
+            if tuple(tap.shape) != (rows, c) or tap.dtype != tdt or tap.device != S["fea"].device:
+                raise ValueError(f"run_trunk_backward: the gradient at {nm} must be {tdt} rows [{rows}, {c}] on {S['fea'].device}, "
+                                 f"got {tuple(tap.shape)} {tap.dtype} on {tap.device}")
+            if not tap.is_contiguous():
+                raise ValueError(f"run_trunk_backward: the gradient at {nm} must be contiguous (strides {tuple(tap.stride())})")
+        self.run_backward(S, None, trunk=(D, taps))
 
     def run_aff_head(self, conv4, conv5, t, dims, N, ps=None):
         """The AffinityNet head as a unit (network/resnet38_aff.py:39-42): the three 1x1 ELU convs of conv4 / conv5 / t = relu(bn7(conv6)) into the
@@ -802,10 +846,11 @@ class Engine:
         return outs, S
 
     # ------------------------------------------------------------------ backward
-    def run_backward(self, S, grads, d_head_rows=None):
+    def run_backward(self, S, grads, d_head_rows=None, trunk=None):
         """grads: per view (g_cam, g_cam_rv, g_fproj, g_rvd) — gradients of the view's four outputs (any may be
         None); in the fused (lowres) path g_cam / g_cam_rv are gradients of the stride-8 maps and `d_head_rows`
-        (joint rows [f_proj | cam | pad]) may be supplied directly.  Accumulates into flat_g."""
+        (joint rows [f_proj | cam | pad]) may be supplied directly.  Accumulates into flat_g.
+        trunk: (D, taps) — run_trunk_backward's entry: the block loop alone, from the gradient D at conv6 and the blocks' input taps."""
         self.finish_packs()                                  # (no-op when the caller already made the transposed packs)
         P = self.packs
         dt = S["dt"]
@@ -873,76 +918,80 @@ class Engine:
             if pair is not None and pw is None:
                 wgrad(*pair)
 
-        # ---- per-view adjoints of the x8 upsamples / gather of the stride-8 gradients
-        d_cam_low, d_rvd = [], []
-        for vw, (g_cam, g_cam_rv, g_fproj, g_rvd) in zip(S["views"], grads):
-            h, w, H, W = vw["h"], vw["w"], vw["H"], vw["W"]
-            if S["lowres"]:
-                d_cam_low.append(g_cam)
-                d_rvd.append(g_cam_rv)
-                continue
-            dc = None
-            if g_cam is not None:
-                dc = torch.empty(N, 21, h, w, device=dev, dtype=torch.float32)
-                L.resize_planar_bwd(g_cam.contiguous().float(), dc, N * 21, h, w, H, W, True)
-            dr = None
-            if g_cam_rv is not None:
-                dr = torch.empty(N, 21, h, w, device=dev, dtype=torch.float32)
-                L.resize_planar_bwd(g_cam_rv.contiguous().float(), dr, N * 21, h, w, H, W, True)
-            if g_rvd is not None:
-                dr = g_rvd.contiguous().float() if dr is None else dr + g_rvd
-            d_cam_low.append(dc)
-            d_rvd.append(dr)
-        # ---- PCM branch -> f9, f8_3, f8_4.  It ends in WEIGHT gradients only (f8_3 / f8_4 read conv4 / conv5 detached, resnet38_contrast.py:63-64),
-        # so nothing of the backbone's backward pass waits for it: it runs on its own stream beside the first blocks (0.5 ms of small kernels + two PCM
-        # launches that otherwise sit in front of the head's data gradient), joined before the gradients are consumed
-        # (same-box A/B against running it in line: 35.25 / 35.16 -> 34.94 / 34.94 ms per step; the b7 launches it overlaps slow down by ~1 %).
-        pcm_stream = None
-        if any(d is not None for d in d_rvd):
-            pcm_stream = self.stream("pcm", dev)
-            pcm_stream.wait_stream(main)
-            with torch.cuda.stream(pcm_stream):
-                DN = torch.empty(M, 32, device=dev, dtype=torch.float32)
-                dFh = torch.zeros(M, 192, device=dev, dtype=torch.float32)
-                DNb = torch.empty(M, 32, device=dev, dtype=torch.bfloat16) if S["Fb"] is not None else None
-                DNl = torch.empty(M, 32, device=dev, dtype=torch.bfloat16) if S["Fb"] is not None else None
-                for vw, dr in zip(S["views"], d_rvd):
-                    if dr is None:
-                        continue
+        if trunk is not None:                                # (run_trunk_backward: no PCM branch, no contrast head)
+            D, taps = trunk
+        else:
+            taps = {}
+            # ---- per-view adjoints of the x8 upsamples / gather of the stride-8 gradients
+            d_cam_low, d_rvd = [], []
+            for vw, (g_cam, g_cam_rv, g_fproj, g_rvd) in zip(S["views"], grads):
+                h, w, H, W = vw["h"], vw["w"], vw["H"], vw["W"]
+                if S["lowres"]:
+                    d_cam_low.append(g_cam)
+                    d_rvd.append(g_cam_rv)
+                    continue
+                dc = None
+                if g_cam is not None:
+                    dc = torch.empty(N, 21, h, w, device=dev, dtype=torch.float32)
+                    L.resize_planar_bwd(g_cam.contiguous().float(), dc, N * 21, h, w, H, W, True)
+                dr = None
+                if g_cam_rv is not None:
+                    dr = torch.empty(N, 21, h, w, device=dev, dtype=torch.float32)
+                    L.resize_planar_bwd(g_cam_rv.contiguous().float(), dr, N * 21, h, w, H, W, True)
+                if g_rvd is not None:
+                    dr = g_rvd.contiguous().float() if dr is None else dr + g_rvd
+                d_cam_low.append(dc)
+                d_rvd.append(dr)
+            # ---- PCM branch -> f9, f8_3, f8_4.  It ends in WEIGHT gradients only (f8_3 / f8_4 read conv4 / conv5 detached, resnet38_contrast.py:63-64),
+            # so nothing of the backbone's backward pass waits for it: it runs on its own stream beside the first blocks (0.5 ms of small kernels + two PCM
+            # launches that otherwise sit in front of the head's data gradient), joined before the gradients are consumed
+            # (same-box A/B against running it in line: 35.25 / 35.16 -> 34.94 / 34.94 ms per step; the b7 launches it overlaps slow down by ~1 %).
+            pcm_stream = None
+            if any(d is not None for d in d_rvd):
+                pcm_stream = self.stream("pcm", dev)
+                pcm_stream.wait_stream(main)
+                with torch.cuda.stream(pcm_stream):
+                    DN = torch.empty(M, 32, device=dev, dtype=torch.float32)
+                    dFh = torch.zeros(M, 192, device=dev, dtype=torch.float32)
+                    DNb = torch.empty(M, 32, device=dev, dtype=torch.bfloat16) if S["Fb"] is not None else None
+                    DNl = torch.empty(M, 32, device=dev, dtype=torch.bfloat16) if S["Fb"] is not None else None
+                    for vw, dr in zip(S["views"], d_rvd):
+                        if dr is None:
+                            continue
+                        off, hw = vw["off"], vw["h"] * vw["w"]
+                        if S["Fb"] is not None:
+                            L.pcm_backward_bf16(S["Fb"][off:], S["Gb"][off:], S["Gl"][off:], dr.contiguous(), vw["rvd"], vw["den"], DN[off:], DNb[off:],
+                                                DNl[off:], dFh[off:], N, hw)
+                        else:
+                            L.pcm_backward(S["Fh"][off:], S["G"][off:], dr.contiguous(), vw["rvd"], vw["den"], DN[off:], dFh[off:], N, hw)
+                    dF = E(M, 192)
+                    L.l2norm_backward(S["Fm"], 192, dFh, S["nrm"], dF, 192, M)
+                    # feature rows are [f8_3 64 | f8_4 128 | x_s 3 | pad], f9.weight's columns [x_s | f8_3 | f8_4]: the weight-gradient kernel rotates
+                    # its dW columns by 3 and accumulates straight into the flat gradient buffer (no staging tensor, no slice adds)
+                    wgrad(head_conv("f9", FEAT_LD, 192), S["feat"], dF, IC_dw=195, dw_rot=3)
+                    if trainable("f8_3") or trainable("f8_4"):
+                        d_feat = E(M, FEAT_LD)
+                        dgrad(head_conv("f9", FEAT_LD, 192), dF, d_feat, epi=1, mask=S["feat"])
+                        wgrad(head_conv("f8_3", 512, 64), S["conv4"], d_feat, ld_dy=FEAT_LD)
+                        wgrad(head_conv("f8_4", 1024, 128), S["conv5"], d_feat.view(-1)[64:], ld_dy=FEAT_LD)
+            pcm_join[0] = pcm_stream
+            # ---- head
+            if d_head_rows is None:
+                if all(dc is None for dc in d_cam_low) and all(g[2] is None for g in grads):
+                    if pcm_stream is not None:
+                        main.wait_stream(pcm_stream)
+                    return
+                d_head_rows = E(M, HEAD_LD)
+                for vw, dc, g in zip(S["views"], d_cam_low, grads):
                     off, hw = vw["off"], vw["h"] * vw["w"]
-                    if S["Fb"] is not None:
-                        L.pcm_backward_bf16(S["Fb"][off:], S["Gb"][off:], S["Gl"][off:], dr.contiguous(), vw["rvd"], vw["den"], DN[off:], DNb[off:],
-                                            DNl[off:], dFh[off:], N, hw)
-                    else:
-                        L.pcm_backward(S["Fh"][off:], S["G"][off:], dr.contiguous(), vw["rvd"], vw["den"], DN[off:], dFh[off:], N, hw)
-                dF = E(M, 192)
-                L.l2norm_backward(S["Fm"], 192, dFh, S["nrm"], dF, 192, M)
-                # feature rows are [f8_3 64 | f8_4 128 | x_s 3 | pad], f9.weight's columns [x_s | f8_3 | f8_4]: the weight-gradient kernel rotates
-                # its dW columns by 3 and accumulates straight into the flat gradient buffer (no staging tensor, no slice adds)
-                wgrad(head_conv("f9", FEAT_LD, 192), S["feat"], dF, IC_dw=195, dw_rot=3)
-                if trainable("f8_3") or trainable("f8_4"):
-                    d_feat = E(M, FEAT_LD)
-                    dgrad(head_conv("f9", FEAT_LD, 192), dF, d_feat, epi=1, mask=S["feat"])
-                    wgrad(head_conv("f8_3", 512, 64), S["conv4"], d_feat, ld_dy=FEAT_LD)
-                    wgrad(head_conv("f8_4", 1024, 128), S["conv5"], d_feat.view(-1)[64:], ld_dy=FEAT_LD)
-        pcm_join[0] = pcm_stream
-        # ---- head
-        if d_head_rows is None:
-            if all(dc is None for dc in d_cam_low) and all(g[2] is None for g in grads):
-                if pcm_stream is not None:
-                    main.wait_stream(pcm_stream)
-                return
-            d_head_rows = E(M, HEAD_LD)
-            for vw, dc, g in zip(S["views"], d_cam_low, grads):
-                off, hw = vw["off"], vw["h"] * vw["w"]
-                gf = g[2].contiguous().float() if g[2] is not None else None
-                L.head_grad_rows(gf, dc.contiguous() if dc is not None else None, S["head"][off:], d_head_rows[off:], HEAD_LD, N, hw)
-        chead = head_conv("head", 4096, HEAD_LD)
-        if trainable("fc_proj") or trainable("fc8"):          # fc_proj and fc8 are adjacent in flat_g: one [149,4096] block
-            L.conv_wgrad(S["fea"], d_head_rows, self.grad_slice("fc_proj", 149 * 4096), OC_dw=149, dtype=_cdt(dt), **chead.wgrad_kw(N))
-        s7, _ = P["bn"]["bn7"]
-        D = E(M, 4096)
-        dgrad(chead, d_head_rows, D, epi=1, scale=s7, drop=masks["dropout7"] if masks else None, mask=S["fea"])
+                    gf = g[2].contiguous().float() if g[2] is not None else None
+                    L.head_grad_rows(gf, dc.contiguous() if dc is not None else None, S["head"][off:], d_head_rows[off:], HEAD_LD, N, hw)
+            chead = head_conv("head", 4096, HEAD_LD)
+            if trainable("fc_proj") or trainable("fc8"):          # fc_proj and fc8 are adjacent in flat_g: one [149,4096] block
+                L.conv_wgrad(S["fea"], d_head_rows, self.grad_slice("fc_proj", 149 * 4096), OC_dw=149, dtype=_cdt(dt), **chead.wgrad_kw(N))
+            s7, _ = P["bn"]["bn7"]
+            D = E(M, 4096)
+            dgrad(chead, d_head_rows, D, epi=1, scale=s7, drop=masks["dropout7"] if masks else None, mask=S["fea"])
         # ---- blocks, last to first trainable
         for i in range(len(arch.BLOCKS) - 1, -1, -1):
             b = arch.BLOCKS[i]
@@ -957,6 +1006,7 @@ class Engine:
             sa, _ = P["bn"][name + ".bn_branch2a"]
             first_trainable = name == "b3"               # its input comes from the frozen prefix
             c1 = Conv(name + ".conv_branch1", cin, cout, 1, stride, 1, din, dout)
+            tap = taps.get(name)                         # a gradient w.r.t. this block's input t from outside the trunk: r_pre of the launch that writes Din (or tmp)
             if kind == "res":
                 s1, _ = P["bn"][name + ".bn_branch2b1"]
                 c2a = Conv(name + ".conv_branch2a", cin, mid, 3, stride, fd, din, dout)
@@ -976,10 +1026,11 @@ class Engine:
                 if same:
                     dgrad(c2a, du, Din, epi=1, scale=sa, mask=sv["t"], r_post=D, pair=(c2a, sv["t"], du))
                 elif fused_skip:                               # both data gradients into t: 9 taps of du + one K segment of D (+ the skip conv's weight gradient: same D)
-                    dgrad(c2a._replace(name=name + ".skip_fused"), du, Din, in2=D, IC2=cout, epi=1, scale=sa, mask=sv["t"], pair=(c1, sv["t"], D))
+                    dgrad(c2a._replace(name=name + ".skip_fused"), du, Din, in2=D, IC2=cout, epi=1, scale=sa, mask=sv["t"], pair=(c1, sv["t"], D),
+                          r_pre=tap)
                 else:
                     tmp = E(Mi, cin)
-                    dgrad(c1, D, tmp)
+                    dgrad(c1, D, tmp, r_pre=tap)
                     dgrad(c2a, du, Din, epi=1, scale=sa, mask=sv["t"], r_pre=tmp)
                 D = Din
                 block_done(name)
@@ -1000,10 +1051,10 @@ class Engine:
                 Din = E(Mi, cin)
                 if (name + ".skip_fused") in P["wt"]:          # both 1x1 data gradients into t as ONE two-source product (+ the skip conv's weight gradient)
                     dgrad(Conv(name + ".skip_fused", cin, cout, 1, 1, 1, din, dout), D, Din, epi=1, scale=sa, mask=sv["t"], in2=du1, IC2=c4,
-                          pair=(c1, sv["t"], D))
+                          pair=(c1, sv["t"], D), r_pre=tap)
                 else:
                     tmp = E(Mi, cin)
-                    dgrad(c1, D, tmp, pair=(c1, sv["t"], D))
+                    dgrad(c1, D, tmp, pair=(c1, sv["t"], D), r_pre=tap)
                     dgrad(c2a, du1, Din, epi=1, scale=sa, mask=sv["t"], r_pre=tmp)
                 D = Din
                 block_done(name)

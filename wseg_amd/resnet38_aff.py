@@ -1,13 +1,13 @@
-"""Drop-in replacement of the reference's AffinityNet module: `--network wseg_amd.resnet38_aff` (inference only).
+"""Drop-in replacement of the reference's AffinityNet module: `--network wseg_amd.resnet38_aff`.
 
 Mirrors the public contract of network/resnet38_aff.py (+ network/resnet38d.py:104-214): `Net()`, `forward(x, to_dense=False)`
 returning the pair affinities [N, P, n_from] (or, with to_dense, the dense [area, area] matrix of one image as a device tensor),
 `.normalize`, `.get_parameter_groups()`, and the reference's state_dict keys (the backbone, then f8_3, f8_4, f8_5, f9).  The
 sub-modules are parameter containers: the backbone runs through wseg_amd.engine (the contrast net's kernels and packs), the
-ELU head on the implicit-GEMM conv (epilogue 3; Engine.run_aff_head), the pairs / dense scatter in csrc/affinity.hip.  Of training
-(aff_train.py) the head exists on its own — wseg_amd/aff_head.py: its training-mode forward and its backward down to conv4 / conv5 /
-conv6, fed by wseg_amd/aff_loss.py — but the backbone cannot take those gradients yet, so a forward of the whole
-net in training mode still raises.
+ELU head on the implicit-GEMM conv (epilogue 3; Engine.run_aff_head), the pairs / dense scatter in csrc/affinity.hip.  `forward` is
+inference: in training mode it raises.  Training (aff_train.py) enters through names of its own: `train_forward` / `train_backward` (the
+saved backbone pass and the ELU head of wseg_amd/aff_head.py; the head's backward, then Engine.run_trunk_backward with the conv4 / conv5
+gradients as taps), which wseg_amd.aff_train.AffTrainer drives without autograd, and `affinities_train`, their differentiable wrapper.
 """
 import os
 
@@ -55,6 +55,33 @@ def indices_of_pairs(radius, size):
     ind_from = full[:ch, rf:rf + cw].reshape(-1)
     ind_to = np.concatenate([full[dy:dy + ch, rf + dx:rf + dx + cw].reshape(-1) for dy, dx in pair_offsets(radius)])
     return ind_from, ind_to
+
+
+def _pair_affinities(f9, N, h, w, r):
+    aff = torch.empty(N, L.aff_num_offsets(r), (h - r + 1) * (w - 2 * r + 2), device=f9.device, dtype=torch.float32)
+    L.aff_pairs(f9, FEAT_C, FEAT_C, aff, N, h, w, r)
+    return aff
+
+
+class _AffinitiesTrain(torch.autograd.Function):
+    """aff = exp(-mean_c |f9[to] - f9[from]|) of the f9 rows of Net.train_forward, with the whole net's backward behind it."""
+
+    @staticmethod
+    def forward(ctx, anchor, f9, saved, N, h, w, r):
+        aff = _pair_affinities(f9, N, h, w, r)
+        ctx.save_for_backward(aff, f9)
+        ctx.saved, ctx.geo = saved, (N, h, w, r)
+        return aff
+
+    @staticmethod
+    def backward(ctx, g):
+        aff, f9 = ctx.saved_tensors
+        N, h, w, r = ctx.geo
+        d_f9 = torch.empty(N * h * w, FEAT_C, device=f9.device, dtype=torch.float32)
+        L.aff_pairs_backward(f9, FEAT_C, FEAT_C, aff, g.contiguous().float(), d_f9, FEAT_C, N, h, w, r)
+        Net.train_backward(ctx.saved, d_f9)
+        ctx.saved = ctx.geo = None
+        return (None,) * 7
 
 
 class Net(nn.Module):
@@ -114,10 +141,57 @@ class Net(nn.Module):
         (h, w), = dims
         r = pair_radius(h, w, self.radius)
         _, f9 = eng.run_aff_head(st["conv4"], st["conv5"], st["t"], dims, N, ps=ps)
-        n_from = (h - r + 1) * (w - 2 * r + 2)
-        aff = torch.empty(N, L.aff_num_offsets(r), n_from, device=x.device, dtype=torch.float32)
-        L.aff_pairs(f9, FEAT_C, FEAT_C, aff, N, h, w, r)
-        return aff, (h, w, r)
+        return _pair_affinities(f9, N, h, w, r), (h, w, r)
+
+    # ---- training (aff_train.py): enters here and through wseg_amd.aff_train, never through forward ----------
+    def set_dropout_masks(self, mask_sets):
+        """Inject Dropout2d scale factors: a list of dicts over the FOUR sites of the backbone (b6 / b7 dropout_2b1, dropout_2b2: this net
+        has no dropout7), one consumed per training pass — the parity tests."""
+        self._engine.injected_masks = list(mask_sets) if mask_sets is not None else None
+
+    def train_forward(self, x):
+        """The training-mode pass down to the f9 rows: backbone with saved activations, then the ELU head.  Returns (f9 rows [M, 448] in
+        the mode's dtype, (h, w, radius), saved) — `saved` goes to train_backward.  No autograd graph, nothing synchronises."""
+        if not self.training:
+            raise RuntimeError("wseg_amd.resnet38_aff: the training pass needs training mode (call .train() first); .eval() has forward / affinities")
+        if not x.is_cuda:
+            raise RuntimeError("wseg_amd.resnet38_aff runs only on an MI355X (HIP) device; there is no CPU fallback")
+        from . import aff_head
+        x = x.contiguous().float()
+        eng = self._engine.active(x.device)
+        st, _ps, S = eng.run_backbone([x], save=True)
+        (h, w), = st["dims"]
+        r = pair_radius(h, w, self.radius)
+        f9, hctx = aff_head.aff_head_forward(self, st["conv4"], st["conv5"], st["t"], x.shape[0], h, w)
+        return f9, (h, w, r), dict(eng=eng, S=S, head=hctx)
+
+    @staticmethod
+    def train_backward(saved, d_f9, gscale=None, between=None):
+        """From d_f9 [M, >= 448] (f32 or the mode's dtype; times the one-element device tensor gscale) to every trainable weight's gradient
+        in the flat buffer: the head's backward, whose f8_5 data gradient folds bn7's scale and ReLU in, then the trunk's with the conv4 /
+        conv5 gradients as taps of b5 / b6.  Gradients ACCUMULATE (the flat buffer is zeroed when it is first attached as the parameters'
+        .grad, and by the optimizer's zero_grad).  between: called between the two phases (scripts/bench_aff_train.py records an event)."""
+        from . import aff_head
+        eng, S = saved["eng"], saved["S"]
+        s7, _ = eng.packs["bn"]["bn7"]
+        d_conv4, d_conv5, d_conv6 = aff_head.aff_head_backward(saved["head"], d_f9, gscale, scale=s7, mask=S["fea"])
+        if between is not None:
+            between()
+        eng.run_trunk_backward(S, d_conv6, {"b5": d_conv4, "b6": d_conv5})
+
+    def affinities_train(self, x):
+        """aff [N, P, n_from] f32 as `affinities` computes it, in training mode and differentiable: its backward (one autograd node) runs
+        aff_pairs_backward, the head's backward and the trunk's, and leaves the gradients in the parameters' .grad (views of the flat
+        buffer).  The reference's loss lines (aff_train.py:111-119) as torch ops on it train the net.  As any autograd gradient these
+        ACCUMULATE over backward calls: clear them with the optimizer's zero_grad (one memset of the flat buffer) or with
+        zero_grad(set_to_none=True) (the next backward re-attaches the views and zeroes the buffer).  With gradients disabled the pass still
+        runs in training mode (dropout masks drawn) but keeps nothing: the saved activations are dropped before it returns."""
+        f9, (h, w, r), saved = self.train_forward(x)
+        if not torch.is_grad_enabled():
+            del saved
+            return _pair_affinities(f9, x.shape[0], h, w, r)
+        anchor = saved["eng"].flat_w.new_zeros((), requires_grad=True)     # the weights live in the flat buffer: keeps the node in the graph
+        return _AffinitiesTrain.apply(anchor, f9, saved, x.shape[0], h, w, r)
 
     def get_parameter_groups(self):
         """network/resnet38_aff.py:100-119."""
@@ -131,7 +205,7 @@ class Net(nn.Module):
         return groups
 
     def train(self, mode=True):
-        """network/resnet38d.py:192-214: frozen prefix + every BatchNorm in eval and frozen (forward still refuses training mode)."""
+        """network/resnet38d.py:192-214: frozen prefix + every BatchNorm in eval and frozen (forward still refuses training mode: see affinities_train)."""
         super().train(mode)
         for layer in self.not_training:
             if isinstance(layer, nn.Conv2d):
