@@ -481,6 +481,28 @@ int wseg_crf_update(const unsigned char* labels, const float* outb, const float*
                     float* Qg, float* Qout, float* logits, unsigned char* amax, int S, int n_labels, int npix, float gt_prob,
                     float w_bilateral, float w_gaussian, void* stream);
 
+/* ---- evaluation counters (eval.py:22-52): integer pixel counts, ADDED into a caller-owned device buffer of unsigned 64-bit cells, so one
+ * buffer collects a whole dataset and is read back once.  Both run on `stream` and synchronise nothing.  The ground-truth axis has
+ * WSEG_EVAL_ROWS = 22 rows: 0..20 the classes, 21 = "a value in 21..254" (the evaluator counts such a pixel towards P of its predicted
+ * class and towards no T or TP); a pixel whose gt is 255 is skipped.  All counting is in integers (32-bit per workgroup in LDS, 64-bit
+ * in the buffer): the result is exact and does not depend on the order of the adds.  n <= 2^40 pixels per call. */
+#define WSEG_EVAL_ROWS 22
+#define WSEG_EVAL_CLASSES 20        /* foreground classes: planes of the curve, the winner axis of its histogram */
+#define WSEG_EVAL_MAX_THR 64
+/* conf[min(gt, 21)][min(pred, 21)] += 1 for every pixel with gt != 255.  pred, gt: uint8 [n] device; conf: u64 [22][22] device. */
+int wseg_eval_confusion(const unsigned char* pred, const unsigned char* gt, long n, unsigned long long* conf, void* stream);
+/* The background-threshold curve in one pass.  Class c (0..19) scores planes[src[c] * plane_stride + i] at pixel i, or 0.0 where
+ * src[c] == -1 (the class is not in the image's dictionary); src: 20 host ints, each in -1..nplanes-1 (planes may be NULL when nplanes
+ * is 0).  Per pixel: m = the largest of the 20 scores, c = the lowest class that attains it, k = the number of thresholds strictly below
+ * m (float32 comparisons), and hist[min(gt, 21)][c][k] += 1.  np.argmax over [t] ++ scores is c + 1 for the thresholds thr[i] with
+ * i < k and 0 for the rest, so suffix sums over k give every threshold's confusion matrix.  All 20 classes absent: m = 0, c = 0.
+ * thr: T HOST floats, non-decreasing, 1 <= T <= WSEG_EVAL_MAX_THR (they travel as a launch argument); hist: u64 [22][20][T+1] device.
+ * NaN scores are out of contract (no out-of-range access, but the cell such a pixel lands in is unspecified); infinities compare as
+ * float32 does.  The workgroup histogram covers only the live winners (the present classes and the first absent one); when that
+ * exceeds 64 KiB of LDS (about 12 present classes at T = 60) the pixels add straight into `hist` with 64-bit global atomics. */
+int wseg_eval_curve(const float* planes, long plane_stride, int nplanes, const int* src, const unsigned char* gt, long n,
+                    const float* thr, int T, unsigned long long* hist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -440,6 +440,33 @@ def rw_pool(cams, src, bg, pooled, H, W, dh, dw):
 def rw_finish(cam_rw, pred, planes, dh, dw, H, W): _call("wseg_rw_finish", _v(cam_rw), _v(pred), planes, dh, dw, H, W)
 
 
+# ---------------------------------------------------------------------------------------------- evaluation counters (csrc/eval.hip)
+EVAL_ROWS, EVAL_CLASSES, EVAL_MAX_THR = 22, 20, 64        # WSEG_EVAL_*
+
+
+def _eval_check(what, counters, cells, n, *u8):
+    """(raw pointers beyond the wrappers below) the counter buffer must be int64 of exactly `cells`, the uint8 buffers hold n pixels"""
+    if torch.is_tensor(counters) and (counters.dtype != torch.int64 or counters.numel() != cells or not counters.is_contiguous()):
+        raise RuntimeError(f"{what}: the counters must be a contiguous int64 tensor of {cells} cells")
+    for t_ in u8:
+        if torch.is_tensor(t_) and (t_.dtype != torch.uint8 or t_.numel() < n or not t_.is_contiguous()):
+            raise RuntimeError(f"{what}: a contiguous uint8 buffer of {n} pixels is expected")
+
+
+def eval_confusion(pred, gt, n, conf):
+    """conf (int64 [22, 22] device, read as u64) += the confusion counts of the uint8 buffers pred / gt [n]."""
+    _eval_check("eval_confusion", conf, EVAL_ROWS * EVAL_ROWS, n, pred, gt)
+    _call("wseg_eval_confusion", _v(pred), _v(gt), C.c_long(n), _v(conf))
+def eval_curve(planes, plane_stride, nplanes, src, gt, n, thr, hist):
+    """src: 20 ints, class c <- planes[src[c] * plane_stride:] (-1: absent, score 0); thr: HOST float32 values, non-decreasing;
+    hist (int64 [22, 20, len(thr) + 1] device, read as u64) += the (gt row, winner, thresholds below the maximum) counts.
+    planes: a float32 tensor, or the device address of plane 0 (views into a larger tensor: the caller vouches for the extent)."""
+    _eval_check("eval_curve", hist, EVAL_ROWS * EVAL_CLASSES * (len(thr) + 1), n, gt)
+    if torch.is_tensor(planes) and (planes.dtype != torch.float32 or planes.numel() < (nplanes - 1) * plane_stride + n):
+        raise RuntimeError(f"eval_curve: planes must be float32 with {nplanes} planes of {n} pixels, {plane_stride} apart")
+    _call("wseg_eval_curve", _v(planes), C.c_long(plane_stride), nplanes, (C.c_int * 20)(*[int(s) for s in src]), _v(gt), C.c_long(n),
+          (C.c_float * len(thr))(*[float(t) for t in thr]), len(thr), _v(hist))
+
 
 # ---------------------------------------------------------------------------------------------- AffinityNet training loss (csrc/aff_loss.hip)
 lib.wseg_aff_loss_workspace_bytes.restype = C.c_long

@@ -17,6 +17,7 @@ import torch
 from . import _lib as L
 from . import data as wdata
 from . import synth
+from .eval import DeviceEval, load_gt
 from .safe_npy import load_pickled_npy
 
 BG_SCORE = 0.27
@@ -78,6 +79,7 @@ def build_parser():
     parser.add_argument("--logt", default=6, type=int)
     parser.add_argument("--crf", default=False, type=bool)
     parser.add_argument("--precision", default=None, choices=[None, "bf16", "fp32", "bf16x3"])
+    parser.add_argument("--gt_dir", default=None, type=str, help="evaluate while inferring: the mIoU of the masks against <gt_dir>/<name>.png")
     return parser
 
 
@@ -110,18 +112,27 @@ def main(argv=None):
         ev.synchronize()
         PIL.Image.fromarray(host.numpy()).save(os.path.join(args.out_rw, name + '.png'))
 
+    ev = DeviceEval("cuda") if args.gt_dir is not None else None       # --gt_dir: confusion counts of every mask, on the device until the end
     pending = None
     for name, img in loader:
         name = name[0]
         H, W = img.shape[2], img.shape[3]
         cam = load_pickled_npy(os.path.join(args.cam_dir, name + '.npy'))
+        gt = load_gt(args.gt_dir, name, (H, W)) if ev is not None else None
         pred = random_walk_image(model, img, cam, (H, W), args.beta, args.logt)
+        if gt is not None:
+            ev.add_masks(pred, torch.from_numpy(gt).pin_memory().to(pred.device, non_blocking=True))
         item = start(name, pred)
         if pending is not None:
             finish(pending)
         pending = item
     if pending is not None:
         finish(pending)
+    if ev is None:
+        return None
+    res = ev.mask_result()
+    print('mIoU: %.3f' % res['mIoU'])
+    return res
 
 
 if __name__ == '__main__':

@@ -15,6 +15,7 @@ import torch
 from . import data as wdata
 from . import synth
 from .crf import crf_inference, labels_from_cams
+from .eval import DeviceEval, curve_lines, load_gt
 from .infer import infer_image
 
 CRF_BG_SCORE, CRF_BILATERAL, CRF_GAUSSIAN, CRF_T = 0.26, (50, 5, 10), (3, 3), 10        # contrast_infer.py:104, 121-122, 113
@@ -41,6 +42,8 @@ def build_parser():
     parser.add_argument("--crf_iters", default=10, type=float)
     parser.add_argument("--labels", default="voc12/cls_labels.npy", type=str)
     parser.add_argument("--precision", default=None, choices=[None, "bf16", "fp32", "bf16x3"])
+    parser.add_argument("--gt_dir", default=None, type=str,
+                        help="evaluate while inferring: <gt_dir>/<name>.png -> the 60-threshold CAM curve, the mIoU of the arg-max masks (and of the CRF masks)")
     return parser
 
 
@@ -93,22 +96,46 @@ def main(argv=None):
     for d in (args.out_cam, args.out_cam_pred, args.out_crf):
         if d is not None:
             os.makedirs(d, exist_ok=True)
+    # --gt_dir: the evaluator's counters are fed from the device tensors of each image (wseg_amd.eval.DeviceEval: one kernel per add, no
+    # synchronisation, read back once after the loop), so the background score can be chosen without writing a single dictionary
+    ev_curve = ev_pred = ev_crf = None
+    if args.gt_dir is not None:
+        ev_curve, ev_pred = DeviceEval("cuda"), DeviceEval("cuda")
+        ev_crf = DeviceEval("cuda") if args.out_crf is not None else None
     pending = None
     for it, (img_name, img_list, label) in enumerate(loader):
         img_name, label = img_name[0], label[0]
         with PIL.Image.open(wdata.get_img_path(img_name, args.voc12_root)) as im:      # (header only: the reference decodes the image again for its shape)
             W, H = im.size
             rgb = np.array(im.convert("RGB")) if args.out_crf is not None else None
+        gt = load_gt(args.gt_dir, img_name, (H, W)) if args.gt_dir is not None else None
         norm_cam, pred, cam_dict = infer_image(model, img_list, label, (H, W), args.out_cam_pred_alpha)
         crf_pred = None
         if rgb is not None:
             crf_pred = crf_prediction(torch.from_numpy(rgb).pin_memory().to(pred.device, non_blocking=True), cam_dict)
+        if gt is not None:
+            gt = torch.from_numpy(gt).pin_memory().to(pred.device, non_blocking=True)
+            ev_curve.add_cams(cam_dict, gt)
+            ev_pred.add_masks(pred, gt)
+            if crf_pred is not None:
+                ev_crf.add_masks(crf_pred, gt)
         item = start(img_name, pred, cam_dict, crf_pred)
         if pending is not None:
             finish(pending)
         pending = item
     if pending is not None:
         finish(pending)
+    if ev_curve is None:
+        return None
+    mious = [r['mIoU'] for r in ev_curve.curve_results()]
+    lines, best = curve_lines(mious)
+    print('\n'.join(lines))
+    print('best background score: %.3f\tmIoU: %.3f%%' % best)
+    out = {'curve': mious, 'best': best, 'pred': ev_pred.mask_result(), 'crf': ev_crf.mask_result() if ev_crf is not None else None}
+    print('cam_pred (alpha %.2f) mIoU: %.3f' % (args.out_cam_pred_alpha, out['pred']['mIoU']))
+    if out['crf'] is not None:
+        print('crf mIoU: %.3f' % out['crf']['mIoU'])
+    return out
 
 
 if __name__ == '__main__':
