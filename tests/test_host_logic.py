@@ -169,6 +169,38 @@ def test_gradient_buckets_tile_the_flat_buffer():
                 assert blk in done or blk in ("fc_proj", "fc8", "f8_3", "f8_4", "f9"), (trigger, name)
 
 
+def test_block_launch_convs_restate_nothing():
+    """engine.block_launch_convs is arch.block_convs with dims: the same (name, cin, cout, k, stride, dilation) set for every block, and
+    launch geometry (IH, IW / OH, OW / pad / the second view's row segment) equal to what block_out_dims gives, worked out here on
+    its own: the strided first conv maps the block's input dims to its output dims, every other conv output dims to output dims."""
+    from wseg_amd import arch
+    from wseg_amd.engine import block_launch_convs
+    N = 2
+    dims = [(104, 72), (40, 56)]
+    for b in arch.BLOCKS:
+        odims = arch.block_out_dims(b, dims)
+        table = arch.block_convs(b)
+        got = block_launch_convs(b, dims, odims)
+        assert {(c.name, c.cin, c.cout, c.k, c.stride, c.dil) for c in got.values()} == set(table), b[0]
+        assert {b[0] + ".conv_" + short for short in got} == {t[0] for t in table}, b[0]
+        assert ("branch1" in got) == (not arch.block_same_shape(b)), b[0]
+        for (name, cin, cout, k, stride, dil) in table:
+            c = got[name.split(".conv_")[1]]
+            first = name.endswith("conv_branch2a") or name.endswith("conv_branch1")       # the convs that read the block's input
+            di = dims if first else odims
+            kw = c.fwd_kw(N)
+            assert (kw["IH"], kw["IW"], kw["OH"], kw["OW"]) == (di[0][0], di[0][1], odims[0][0], odims[0][1]), name
+            assert kw["seg2"] == (di[1][0], di[1][1], odims[1][0], odims[1][1]), name
+            assert kw["pad"] == dil * (k // 2) and (kw["KH"], kw["KW"], kw["stride"], kw["dil"]) == (k, k, stride, dil), name
+            assert (kw["N"], kw["IC"], kw["OC"]) == (N, cin, cout), name
+            if not first:
+                assert stride == 1, name
+            # the conv's own arithmetic on its input dims gives the block's output dims
+            assert [((h + 2 * kw["pad"] - dil * (k - 1) - 1) // stride + 1, (w + 2 * kw["pad"] - dil * (k - 1) - 1) // stride + 1) for (h, w) in di] == odims, name
+        dims = odims
+    assert dims == [(13, 9), (5, 7)]
+
+
 def test_eval_matches_the_reference_evaluator(golden_dir, tmp_path, lib):
     """wseg_amd.eval.do_eval against IoU tables produced by the reference's own eval.py:13-86 (`do_python_eval`, run by
     oracle/make_goldens.py on the inputs stored in the fixture): png predictions and npy CAM dictionaries at three background

@@ -60,11 +60,26 @@ class Conv(NamedTuple):
     wgrad_kw = fwd_kw                                       # (x over din, dY over dout: the forward geometry)
 
 
-class _Pass:
-    """What the launches of one pass share: batch size, device, precision mode and packs."""
+def block_launch_convs(b, din, dout):
+    """The convs of block `b` (an arch.BLOCKS row) as launch descriptors, keyed by short name: branch2a, branch2b1, branch2b2 (bottleneck),
+    branch1 (absent in a same-shape ResBlock).  Name, channels, kernel, stride and dilation are arch.block_convs(b)'s; the two convs that
+    read the block's input (branch2a, the strided one, and the skip conv branch1) map din -> dout, the others dout -> dout."""
+    return {name.split(".conv_")[1]: Conv(name, cin, cout, k, stride, dil, din if name.endswith(("branch2a", "branch1")) else dout, dout)
+            for (name, cin, cout, k, stride, dil) in arch.block_convs(b)}
 
-    def __init__(self, N, dev, dt, P):
-        self.N, self.dev, self.dt, self.P = N, dev, dt, P
+
+def head_conv(name, cin, cout, dims):                        # a head layer: a 1x1 conv on the stride-8 maps
+    return Conv(name, cin, cout, 1, 1, 1, dims, dims)
+
+
+class _Pass:
+    """What the launches of one pass share: batch size, device, precision mode, packs, and the launch helpers — `conv` of a forward pass; `wgrad`,
+    `dgrad`, `block_done` of a backward pass (Engine._begin_backward), with its streams: `main`, and `side`, the PCM branch's until main has waited for it."""
+
+    def __init__(self, eng, N, dev, dt, P):
+        self.eng, self.N, self.dev, self.dt, self.P = eng, N, dev, dt, P
+        self.main = self.side = None
+        self.planes = {}                                     # split-bf16 mode: (hi, lo) bf16 planes of an f32 operand, made once per tensor
 
     def rows_of(self, dims):
         return sum(self.N * h * w for (h, w) in dims)
@@ -81,6 +96,59 @@ class _Pass:
 
     def conv(self, c, inp, out, out2=None, **kw):
         L.conv_igemm(inp, self.P["w"][c.name], out, out2, dtype=_cdt(self.dt), **c.fwd_kw(self.N), **kw)
+
+    def trainable(self, nm):
+        return self.eng.conv_param(nm).requires_grad
+
+    def split(self, t_):
+        key = (t_.data_ptr(), t_.numel())
+        if key not in self.planes:
+            hi, lo = torch.empty(t_.shape, device=self.dev, dtype=torch.bfloat16), torch.empty(t_.shape, device=self.dev, dtype=torch.bfloat16)
+            L.split_bf16(t_, hi, lo)
+            self.planes[key] = (hi, lo, t_)                  # (keeps the source alive: the key is its address)
+        return self.planes[key][:2]
+
+    def wgrad(self, c, x, dy, **kw):
+        """dW of conv `c` accumulated into its slice of flat_g (nothing when the parameter is frozen)"""
+        if not self.trainable(c.name):
+            return
+        dw = self.eng.grad_slice(c.name)
+        args = dict(c.wgrad_kw(self.N), dtype=_cdt(self.dt), **kw)
+        if self.dt == L.F32X3 and c.cin >= 256 and c.cout >= 256 and not kw and x.is_contiguous() and dy.is_contiguous() \
+                and x.shape[1] == c.cin and dy.shape[1] == c.cout:
+            # split-bf16 products on the bf16 pixel-reduction kernel: dW += X_lo^T dY_hi + X_hi^T dY_lo + X_hi^T dY_hi (it accumulates
+            # with float atomics anyway) — 3 launches at the bf16 kernel's rate beat one launch of the f32-tile kernel that splits inside
+            (xh, xl), (dh, dl) = self.split(x), self.split(dy)
+            args["dtype"] = None
+            L.conv_wgrad(xl, dh, dw, **args)
+            L.conv_wgrad(xh, dl, dw, **args)
+            L.conv_wgrad(xh, dh, dw, **args)
+        else:
+            L.conv_wgrad(x, dy, dw, **args)
+
+    def block_done(self, nm):
+        """All weight gradients of block `nm` are enqueued: the data-parallel trainer may start reducing its bucket."""
+        if self.eng.block_done_hook is not None:
+            if self.side is not None:                        # the last bucket (b7 + heads) holds the PCM branch's f9 / f8_3 / f8_4 gradients
+                self.main.wait_stream(self.side)
+                self.side = None
+            self.eng.block_done_hook(nm)
+
+    def dgrad(self, c, dy, out, pair=None, **kw):
+        """dX of conv `c`.  pair = (conv, x, dy): a weight gradient of the same dY, launched in the same grid in bf16 mode
+        (wseg_conv_bwd_pair) and on its own behind this launch otherwise."""
+        pw = None
+        if pair is not None and self.dt == L.BF16 and self.trainable(pair[0].name):
+            pc, px, pdy = pair
+            pw = (px, pdy, self.eng.grad_slice(pc.name), dict(pc.wgrad_kw(self.N), dtype=_cdt(self.dt)))
+        L.conv_igemm(dy, self.P["wt"][c.name], out, None, dtype=_cdt(self.dt), pair_wgrad=pw, **c.dgrad_kw(self.N), **kw)
+        if pair is not None and pw is None:
+            self.wgrad(*pair)
+
+    def end_backward(self):
+        self.planes.clear()
+        if self.side is not None:
+            self.main.wait_stream(self.side)
 
 
 class Engine:
@@ -559,14 +627,11 @@ class Engine:
 
     def _run_blocks(self, xs, state, first, last, save, S, final_t=None):
         """Blocks arch.BLOCKS[first:last] (first == 0: conv1a first) over the batched views.  state: the dict an earlier call returned."""
-        net = self.net
-        V = len(xs)
-        dev = xs[0].device
-        dt = DT_OF[net.precision]
+        V, dev, N = len(xs), xs[0].device, xs[0].shape[0]
+        dt = DT_OF[self.net.precision]
         P = self.ensure_packs(dev, dt)
-        N = xs[0].shape[0]
         masks = S["masks"] if S is not None else None
-        ps = _Pass(N, dev, dt, P)
+        ps = _Pass(self, N, dev, dt, P)
         E, conv, rows_of = ps.E, ps.conv, ps.rows_of
 
         def next_bn(i):
@@ -595,24 +660,23 @@ class Engine:
             nxt_same = i + 1 < len(arch.BLOCKS) and arch.block_same_shape(arch.BLOCKS[i + 1])
             odims = arch.block_out_dims(b, dims)
             Mo = rows_of(odims)
-            skip = Conv(name + ".conv_branch1", cin, cout, 1, stride, 1, dims, odims)
+            cv = block_launch_convs(b, dims, odims)
             if kind == "res":
                 s1, sh1 = P["bn"][name + ".bn_branch2b1"]
                 v = E(Mo, mid)
-                conv(Conv(name + ".conv_branch2a", cin, mid, 3, stride, fd, dims, odims), t, None, v, scale=s1, shift=sh1)
+                conv(cv["branch2a"], t, None, v, scale=s1, shift=sh1)
                 xn = E(Mo, cout) if nxt_same else None
                 tn = final_t if (final_t is not None and i == last - 1) else E(Mo, cout)
                 assert tn.shape == (Mo, cout) and tn.dtype == L.TORCH_DTYPE[dt]
-                c2b1 = Conv(name + ".conv_branch2b1", mid, cout, 3, 1, d, odims, odims)
-                if (name + ".skip_fused") in P["w"]:            # last conv + 1x1 skip conv as one two-source launch
-                    conv(c2b1._replace(name=name + ".skip_fused"), v, xn, tn, in2=t, IC2=cin, scale=nsc, shift=nsh, drop=ndrop)
+                if (name + ".skip_fused") in P["w"]:            # branch2b1 + the 1x1 skip conv branch1 as one two-source launch: nine taps of v, then one K segment of t
+                    conv(cv["branch2b1"]._replace(name=name + ".skip_fused"), v, xn, tn, in2=t, IC2=cin, scale=nsc, shift=nsh, drop=ndrop)
                 else:
                     if same:
                         rpost = xraw
                     else:
                         rpost = E(Mo, cout)
-                        conv(skip, t, rpost)
-                    conv(c2b1, v, xn, tn, r_post=rpost, scale=nsc, shift=nsh, drop=ndrop)
+                        conv(cv["branch1"], t, rpost)
+                    conv(cv["branch2b1"], v, xn, tn, r_post=rpost, scale=nsc, shift=nsh, drop=ndrop)
                 if save:
                     S[name] = dict(t=t, v=v)
             else:
@@ -622,22 +686,20 @@ class Engine:
                 d1 = masks[name + ".dropout_2b1"] if masks else None
                 d2 = masks[name + ".dropout_2b2"] if masks else None
                 v1 = E(Mo, c4)
-                conv(Conv(name + ".conv_branch2a", cin, c4, 1, stride, 1, dims, odims), t, None, v1, scale=s1, shift=sh1, drop=d1)
+                conv(cv["branch2a"], t, None, v1, scale=s1, shift=sh1, drop=d1)
                 v2 = E(Mo, c2)
-                conv(Conv(name + ".conv_branch2b1", c4, c2, 3, 1, d, odims, odims), v1, None, v2, scale=s2, shift=sh2, drop=d2)
+                conv(cv["branch2b1"], v1, None, v2, scale=s2, shift=sh2, drop=d2)
                 xn = None
                 tn = E(Mo, cout)
-                if (name + ".skip_fused") in P["w"]:            # out = [t | v2] . [W_branch1 | W_branch2b2]^T in one launch
-                    conv(Conv(name + ".skip_fused", cin, cout, 1, 1, 1, odims, odims), t, xn, tn, in2=v2, scale=nsc, shift=nsh, drop=ndrop)
+                if (name + ".skip_fused") in P["w"]:            # branch1 + branch2b2 in one launch: out = [t | v2] . [W_branch1 | W_branch2b2]^T (stride 1: din == dout)
+                    conv(cv["branch1"]._replace(name=name + ".skip_fused"), t, xn, tn, in2=v2, scale=nsc, shift=nsh, drop=ndrop)
                 else:
                     b1 = E(Mo, cout)
-                    conv(skip, t, b1)
-                    conv(Conv(name + ".conv_branch2b2", c2, cout, 1, 1, 1, odims, odims), v2, xn, tn, r_post=b1, scale=nsc, shift=nsh, drop=ndrop)
+                    conv(cv["branch1"], t, b1)
+                    conv(cv["branch2b2"], v2, xn, tn, r_post=b1, scale=nsc, shift=nsh, drop=ndrop)
                 if save:
                     S[name] = dict(t=t, v1=v1, v2=v2)
             sdims[name] = (dims, odims)
-            if S is not None:
-                S["dims"][name] = (dims, odims)
             if name == "b5":
                 conv4 = t
             if name == "b6":
@@ -665,32 +727,44 @@ class Engine:
     def run_backbone(self, xs, save=False):
         """conv1a and every block, no head (the AffinityNet puts its own on top).  Returns (state, pass): state["t"] = relu(bn7(conv6)),
         state["conv4"] / ["conv5"] the inputs of b5 / b6, state["dims"] the stride-8 dims; `pass.conv` launches on the current packs.
-        save: returns (state, pass, S) — S is the context run_trunk_backward takes: the trainable blocks' activations as run_forward
-        stores them, dims, N, dt and the four block masks (drawn in training mode, or injected; the AffinityNet has no dropout7: that site
-        is present as None), with S["fea"] = state["t"] (bn7's ReLU mask)."""
+        save: returns (state, pass, S) — S is the context run_trunk_backward takes (_run_trunk), with the four block masks."""
         if not save:
-            st = self._run_blocks(xs, None, 0, len(arch.BLOCKS), False, None)
-            self._join_late_packs(xs[0].device)
-            return st, _Pass(st["N"], xs[0].device, st["dt"], self.packs)
+            return self._run_trunk(xs, False, None)[:2]
         assert len(xs) == 1, "the saved backbone pass takes one view"
-        dev, N = xs[0].device, xs[0].shape[0]
+        return self._run_trunk(xs, True, self.MASK_SPECS[:4])
+
+    def _run_trunk(self, xs, save, mask_specs, prefix=None, keep_frozen=False):
+        """The trunk's forward pass, the one entry of run_forward and run_backbone: conv1a and the frozen blocks (or the caller's `prefix`), the
+        trainable blocks, the late packs joined.  mask_specs: the Dropout2d sites that get a mask in training mode — MASK_SPECS, its first four
+        (the AffinityNet backbone has no dropout7: that site is present as None), or None: no dropout in any mode.  keep_frozen: the frozen
+        blocks' activations are saved too (the tests' gate capture).  Returns (state of _run_blocks, pass, S), S the context, created here only:
+          always: masks {site: [V*N, C] scales} or None, dims {block: (input dims, output dims)}, N, V, dt, xs
+          save, read by the trunk's backward (with masks, dims, N, dt): per trainable block S[name] = {t, v} (ResBlock) or {t, v1, v2} (bottleneck),
+            its input relu(bn_branch2a(x)) and the inputs of its later convs; fea = relu(bn7(conv6)) (. dropout7), bn7's ReLU mask; hdims, M
+          save, read by the contrast backward only: conv4, conv5 (the inputs of b5 / b6), and what run_forward adds: lowres, head, feat, G, Fm,
+            Fh, Fb, Gb, Gl, nrm, views"""
+        V, dev, N = len(xs), xs[0].device, xs[0].shape[0]
         dt = DT_OF[self.net.precision]
-        self.ensure_packs(dev, dt)
-        masks = self._masks(N, 1, dev, self.MASK_SPECS[:4])
-        if masks is not None:
+        P = self.ensure_packs(dev, dt)
+        masks = self._masks(N, V, dev, mask_specs) if mask_specs else None
+        if masks is not None and len(mask_specs) == 4:
             assert "dropout7" not in masks, "the AffinityNet backbone has four Dropout2d sites: injected masks carry no dropout7"
             masks["dropout7"] = None
-        S = {"masks": masks, "dims": {}, "N": N, "V": 1, "dt": dt, "xs": xs}
-        prefix = self._run_blocks(xs, None, 0, arch.N_FROZEN_BLOCKS, False, None)      # (the frozen blocks keep nothing)
-        S["dims"].update(prefix["sdims"])
-        st = self._run_blocks(xs, prefix, arch.N_FROZEN_BLOCKS, len(arch.BLOCKS), True, S)
+        S = {"masks": masks, "dims": {}, "N": N, "V": V, "dt": dt, "xs": xs}
+        if prefix is None:
+            prefix = self._run_blocks(xs, None, 0, arch.N_FROZEN_BLOCKS, keep_frozen, S if keep_frozen else None)
+        assert prefix["N"] == N and prefix["V"] == V and prefix["dt"] == dt and prefix["in_dims"] == [tuple(x.shape[2:]) for x in xs], \
+            "the prefix was computed for another batch shape / precision"
+        st = self._run_blocks(xs, prefix, arch.N_FROZEN_BLOCKS, len(arch.BLOCKS), save, S)
+        S["dims"].update(prefix["sdims"], **st["sdims"])
         self._join_late_packs(dev)
-        ps = _Pass(N, dev, dt, self.packs)
-        S.update(fea=st["t"], hdims=st["dims"], M=ps.rows_of(st["dims"]), conv4=st["conv4"], conv5=st["conv5"])
+        ps = _Pass(self, N, dev, dt, P)
+        if save:
+            S.update(fea=st["t"], hdims=st["dims"], M=ps.rows_of(st["dims"]), conv4=st["conv4"], conv5=st["conv5"])
         return st, ps, S
 
     def run_trunk_backward(self, S, D, taps=None):
-        """The backbone's backward on its own: the block loop of run_backward from D [M, 4096], the gradient at conv6 BEFORE bn7 (aff_head_backward's
+        """The backbone's backward on its own: _trunk_backward, checked, from D [M, 4096], the gradient at conv6 BEFORE bn7 (aff_head_backward's
         d_t with scale = bn7's scale and mask = t), on the context S of run_backbone(save=True).  taps {"b5": d_conv4, "b6": d_conv5}: gradients
         w.r.t. those blocks' input t = relu(bn_branch2a(x)) (pixel rows in the mode's dtype), added before the block's mask . scale.  Weight
         gradients accumulate into flat_g, block_done fires as in run_backward; the PCM and contrast-head sections do not run."""
@@ -710,7 +784,9 @@ class Engine:
                                  f"got {tuple(tap.shape)} {tap.dtype} on {tap.device}")
             if not tap.is_contiguous():
                 raise ValueError(f"run_trunk_backward: the gradient at {nm} must be contiguous (strides {tuple(tap.stride())})")
-        self.run_backward(S, None, trunk=(D, taps))
+        ps = self._begin_backward(S)
+        self._trunk_backward(ps, S, dict(taps, conv6=D))
+        ps.end_backward()
 
     def run_aff_head(self, conv4, conv5, t, dims, N, ps=None):
         """The AffinityNet head as a unit (network/resnet38_aff.py:39-42): the three 1x1 ELU convs of conv4 / conv5 / t = relu(bn7(conv6)) into the
@@ -720,12 +796,12 @@ class Engine:
             dev = t.device
             P = self.ensure_packs(dev, DT_OF[self.net.precision])
             self._join_late_packs(dev)
-            ps = _Pass(N, dev, DT_OF[self.net.precision], P)
+            ps = _Pass(self, N, dev, DT_OF[self.net.precision], P)
         M = ps.rows_of(dims)
         C = AFF_FEAT_C
 
         def conv(inp, name, out, cin, cout):                  # 1x1 conv + ELU into a column slice of `out`
-            ps.conv(Conv(name, cin, cout, 1, 1, 1, dims, dims), inp, out, epi=3, ld_out=C)
+            ps.conv(head_conv(name, cin, cout, dims), inp, out, epi=3, ld_out=C)
 
         feat = ps.E(M, C)
         for name, inp in (("f8_3", conv4), ("f8_4", conv5), ("f8_5", t)):
@@ -759,38 +835,18 @@ class Engine:
         matrix [rows(view 1) ++ rows(view 2)][C] and every conv / wgrad is ONE launch over both row segments
         (the 128x128 view alone cannot fill the chip).  Returns ([per-view output tuple], saved context).
         prefix: the result of run_prefix(xs) when the caller has already computed it."""
-        net = self.net
-        V = len(xs)
-        assert V in (1, 2)
-        dev = xs[0].device
-        dt = DT_OF[net.precision]
-        P = self.ensure_packs(dev, dt)
-        N = xs[0].shape[0]
-        assert all(x.shape[0] == N for x in xs)
-        masks = self._masks(N, V, dev)
-        S = {"masks": masks, "dims": {}, "N": N, "V": V, "dt": dt, "xs": xs, "lowres": lowres}
-        if prefix is None:                                    # (the frozen blocks' activations are kept only for the tests' gate capture)
-            prefix = self._run_blocks(xs, None, 0, arch.N_FROZEN_BLOCKS, save and self.capture_ctx, S if (save and self.capture_ctx) else None)
-        assert prefix["N"] == N and prefix["V"] == V and prefix["dt"] == dt and prefix["in_dims"] == [tuple(x.shape[2:]) for x in xs], \
-            "run_forward: the prefix was computed for another batch shape / precision"
-        S["dims"].update(prefix["sdims"])
-        st = self._run_blocks(xs, prefix, arch.N_FROZEN_BLOCKS, len(arch.BLOCKS), save, S)
-        t, dims, conv4, conv5 = st["t"], st["dims"], st["conv4"], st["conv5"]
-        ps = _Pass(N, dev, dt, P)
+        assert len(xs) in (1, 2) and all(x.shape[0] == xs[0].shape[0] for x in xs)
+        st, ps, S = self._run_trunk(xs, save, self.MASK_SPECS, prefix, keep_frozen=save and self.capture_ctx)
+        S["lowres"] = lowres
+        N, dev, dt = ps.N, ps.dev, ps.dt
+        fea, dims, conv4, conv5 = st["t"], st["dims"], st["conv4"], st["conv5"]       # fea: relu(bn7(x)) * dropout7   [M,4096]
         E, conv = ps.E, ps.conv
-
-        def head_conv(nm, cin, cout):                         # the heads are 1x1 convs on the stride-8 maps
-            return Conv(nm, cin, cout, 1, 1, 1, dims, dims)
-
-        fea = t                                               # relu(bn7(x)) * dropout7   [M,4096]
-        self._join_late_packs(dev)
-        M = ps.rows_of(dims)
-        offs = ps.offs_of(dims)
+        M, offs = ps.rows_of(dims), ps.offs_of(dims)
         head = E(M, HEAD_LD)
-        conv(head_conv("head", 4096, HEAD_LD), fea, head, relu_lt=128, w_rows=256)
+        conv(head_conv("head", 4096, HEAD_LD, dims), fea, head, relu_lt=128, w_rows=256)
         feat = E(M, FEAT_LD)
-        conv(head_conv("f8_3", 512, 64), conv4, feat, epi=2, ld_out=FEAT_LD)
-        conv(head_conv("f8_4", 1024, 128), conv5, feat.view(-1)[64:], epi=2, ld_out=FEAT_LD)
+        conv(head_conv("f8_3", 512, 64, dims), conv4, feat, epi=2, ld_out=FEAT_LD)
+        conv(head_conv("f8_4", 1024, 128, dims), conv5, feat.view(-1)[64:], epi=2, ld_out=FEAT_LD)
         G = torch.empty(M, 32, device=dev, dtype=torch.float32)
         views = []
         for x, off, (h, w) in zip(xs, offs, dims):
@@ -802,7 +858,7 @@ class Engine:
             L.pcm_xs(x, feat[off:], FEAT_LD, 192, FEAT_LD, N, x.shape[2], x.shape[3], h, w)
             views.append(dict(h=h, w=w, H=x.shape[2], W=x.shape[3], off=off, rows=N * hw, cam_low=cam_low))
         Fm = E(M, 192)
-        conv(head_conv("f9", FEAT_LD, 192), feat, Fm)
+        conv(head_conv("f9", FEAT_LD, 192, dims), feat, Fm)
         Fh = torch.empty(M, 192, device=dev, dtype=torch.float32)
         nrm = torch.empty(M, device=dev, dtype=torch.float32)
         L.l2norm_forward(Fm, 192, Fh, nrm, M)
@@ -841,158 +897,102 @@ class Engine:
         if save and self.capture_ctx:
             self.last_ctx = S
         if save:
-            S.update(fea=fea, head=head, G=G, feat=feat, Fm=Fm, Fh=Fh, Fb=Fb, Gb=Gb, Gl=Gl, nrm=nrm, conv4=conv4, conv5=conv5,
-                     views=views, hdims=dims, M=M)
+            S.update(head=head, G=G, feat=feat, Fm=Fm, Fh=Fh, Fb=Fb, Gb=Gb, Gl=Gl, nrm=nrm, views=views)
         return outs, S
 
     # ------------------------------------------------------------------ backward
-    def run_backward(self, S, grads, d_head_rows=None, trunk=None):
+    def _begin_backward(self, S):
+        """What every backward pass starts with: the transposed packs (no-op when the caller made them), the gradient views, the pass that launches"""
+        self.finish_packs()
+        self.attach_grads()
+        ps = _Pass(self, S["N"], S["fea"].device, S["dt"], self.packs)
+        ps.main = torch.cuda.current_stream(ps.dev)
+        return ps
+
+    def run_backward(self, S, grads, d_head_rows=None):
         """grads: per view (g_cam, g_cam_rv, g_fproj, g_rvd) — gradients of the view's four outputs (any may be
         None); in the fused (lowres) path g_cam / g_cam_rv are gradients of the stride-8 maps and `d_head_rows`
-        (joint rows [f_proj | cam | pad]) may be supplied directly.  Accumulates into flat_g.
-        trunk: (D, taps) — run_trunk_backward's entry: the block loop alone, from the gradient D at conv6 and the blocks' input taps."""
-        self.finish_packs()                                  # (no-op when the caller already made the transposed packs)
-        P = self.packs
-        dt = S["dt"]
-        N, M = S["N"], S["M"]
-        hdims = S["hdims"]
-        dev = S["fea"].device
-        masks = S["masks"]
-        self.attach_grads()
-        ps = _Pass(N, dev, dt, P)
-        E, rows_of = ps.E, ps.rows_of
-
-        def trainable(nm):
-            return self.conv_param(nm).requires_grad
-
-        def head_conv(nm, cin, cout):
-            return Conv(nm, cin, cout, 1, 1, 1, hdims, hdims)
-
-        main = torch.cuda.current_stream(dev)
-        pcm_join = [None]                                    # the PCM branch's stream until main has waited for it
-
-        planes = {}                                          # split-bf16 mode: (hi, lo) bf16 planes of an f32 operand, made once per tensor
-
-        def split(t_):
-            key = (t_.data_ptr(), t_.numel())
-            if key not in planes:
-                hi, lo = torch.empty(t_.shape, device=dev, dtype=torch.bfloat16), torch.empty(t_.shape, device=dev, dtype=torch.bfloat16)
-                L.split_bf16(t_, hi, lo)
-                planes[key] = (hi, lo, t_)                   # (keeps the source alive: the key is its address)
-            return planes[key][:2]
-
-        def wgrad(c, x, dy, **kw):
-            """dW of conv `c` accumulated into its slice of flat_g (nothing when the parameter is frozen)"""
-            if not trainable(c.name):
-                return
-            dw = self.grad_slice(c.name)
-            args = dict(c.wgrad_kw(N), dtype=_cdt(dt), **kw)
-            if dt == L.F32X3 and c.cin >= 256 and c.cout >= 256 and not kw and x.is_contiguous() and dy.is_contiguous() \
-                    and x.shape[1] == c.cin and dy.shape[1] == c.cout:
-                # split-bf16 products on the bf16 pixel-reduction kernel: dW += X_lo^T dY_hi + X_hi^T dY_lo + X_hi^T dY_hi (it accumulates
-                # with float atomics anyway) — 3 launches at the bf16 kernel's rate beat one launch of the f32-tile kernel that splits inside
-                (xh, xl), (dh, dl) = split(x), split(dy)
-                args["dtype"] = None
-                L.conv_wgrad(xl, dh, dw, **args)
-                L.conv_wgrad(xh, dl, dw, **args)
-                L.conv_wgrad(xh, dh, dw, **args)
-            else:
-                L.conv_wgrad(x, dy, dw, **args)
-
-        def block_done(nm):
-            """All weight gradients of block `nm` are enqueued: the data-parallel trainer may start reducing its bucket."""
-            if self.block_done_hook is not None:
-                if pcm_join[0] is not None:                  # the last bucket (b7 + heads) holds the PCM branch's f9 / f8_3 / f8_4 gradients
-                    main.wait_stream(pcm_join[0])
-                    pcm_join[0] = None
-                self.block_done_hook(nm)
-
-        def dgrad(c, dy, out, pair=None, **kw):
-            """dX of conv `c`.  pair = (conv, x, dy): a weight gradient of the same dY, launched in the same grid in bf16 mode
-            (wseg_conv_bwd_pair) and on its own behind this launch otherwise."""
-            pw = None
-            if pair is not None and dt == L.BF16 and trainable(pair[0].name):
-                pc, px, pdy = pair
-                pw = (px, pdy, self.grad_slice(pc.name), dict(pc.wgrad_kw(N), dtype=_cdt(dt)))
-            L.conv_igemm(dy, P["wt"][c.name], out, None, dtype=_cdt(dt), pair_wgrad=pw, **c.dgrad_kw(N), **kw)
-            if pair is not None and pw is None:
-                wgrad(*pair)
-
-        if trunk is not None:                                # (run_trunk_backward: no PCM branch, no contrast head)
-            D, taps = trunk
-        else:
-            taps = {}
-            # ---- per-view adjoints of the x8 upsamples / gather of the stride-8 gradients
-            d_cam_low, d_rvd = [], []
-            for vw, (g_cam, g_cam_rv, g_fproj, g_rvd) in zip(S["views"], grads):
-                h, w, H, W = vw["h"], vw["w"], vw["H"], vw["W"]
-                if S["lowres"]:
-                    d_cam_low.append(g_cam)
-                    d_rvd.append(g_cam_rv)
-                    continue
-                dc = None
-                if g_cam is not None:
-                    dc = torch.empty(N, 21, h, w, device=dev, dtype=torch.float32)
-                    L.resize_planar_bwd(g_cam.contiguous().float(), dc, N * 21, h, w, H, W, True)
-                dr = None
-                if g_cam_rv is not None:
-                    dr = torch.empty(N, 21, h, w, device=dev, dtype=torch.float32)
-                    L.resize_planar_bwd(g_cam_rv.contiguous().float(), dr, N * 21, h, w, H, W, True)
-                if g_rvd is not None:
-                    dr = g_rvd.contiguous().float() if dr is None else dr + g_rvd
-                d_cam_low.append(dc)
-                d_rvd.append(dr)
-            # ---- PCM branch -> f9, f8_3, f8_4.  It ends in WEIGHT gradients only (f8_3 / f8_4 read conv4 / conv5 detached, resnet38_contrast.py:63-64),
-            # so nothing of the backbone's backward pass waits for it: it runs on its own stream beside the first blocks (0.5 ms of small kernels + two PCM
-            # launches that otherwise sit in front of the head's data gradient), joined before the gradients are consumed
-            # (same-box A/B against running it in line: 35.25 / 35.16 -> 34.94 / 34.94 ms per step; the b7 launches it overlaps slow down by ~1 %).
-            pcm_stream = None
-            if any(d is not None for d in d_rvd):
-                pcm_stream = self.stream("pcm", dev)
-                pcm_stream.wait_stream(main)
-                with torch.cuda.stream(pcm_stream):
-                    DN = torch.empty(M, 32, device=dev, dtype=torch.float32)
-                    dFh = torch.zeros(M, 192, device=dev, dtype=torch.float32)
-                    DNb = torch.empty(M, 32, device=dev, dtype=torch.bfloat16) if S["Fb"] is not None else None
-                    DNl = torch.empty(M, 32, device=dev, dtype=torch.bfloat16) if S["Fb"] is not None else None
-                    for vw, dr in zip(S["views"], d_rvd):
-                        if dr is None:
-                            continue
-                        off, hw = vw["off"], vw["h"] * vw["w"]
-                        if S["Fb"] is not None:
-                            L.pcm_backward_bf16(S["Fb"][off:], S["Gb"][off:], S["Gl"][off:], dr.contiguous(), vw["rvd"], vw["den"], DN[off:], DNb[off:],
-                                                DNl[off:], dFh[off:], N, hw)
-                        else:
-                            L.pcm_backward(S["Fh"][off:], S["G"][off:], dr.contiguous(), vw["rvd"], vw["den"], DN[off:], dFh[off:], N, hw)
-                    dF = E(M, 192)
-                    L.l2norm_backward(S["Fm"], 192, dFh, S["nrm"], dF, 192, M)
-                    # feature rows are [f8_3 64 | f8_4 128 | x_s 3 | pad], f9.weight's columns [x_s | f8_3 | f8_4]: the weight-gradient kernel rotates
-                    # its dW columns by 3 and accumulates straight into the flat gradient buffer (no staging tensor, no slice adds)
-                    wgrad(head_conv("f9", FEAT_LD, 192), S["feat"], dF, IC_dw=195, dw_rot=3)
-                    if trainable("f8_3") or trainable("f8_4"):
-                        d_feat = E(M, FEAT_LD)
-                        dgrad(head_conv("f9", FEAT_LD, 192), dF, d_feat, epi=1, mask=S["feat"])
-                        wgrad(head_conv("f8_3", 512, 64), S["conv4"], d_feat, ld_dy=FEAT_LD)
-                        wgrad(head_conv("f8_4", 1024, 128), S["conv5"], d_feat.view(-1)[64:], ld_dy=FEAT_LD)
-            pcm_join[0] = pcm_stream
-            # ---- head
-            if d_head_rows is None:
-                if all(dc is None for dc in d_cam_low) and all(g[2] is None for g in grads):
-                    if pcm_stream is not None:
-                        main.wait_stream(pcm_stream)
-                    return
-                d_head_rows = E(M, HEAD_LD)
-                for vw, dc, g in zip(S["views"], d_cam_low, grads):
+        (joint rows [f_proj | cam | pad]) may be supplied directly.  Accumulates into flat_g."""
+        ps = self._begin_backward(S)
+        P, dt, dev, N, M, hdims, masks = ps.P, ps.dt, ps.dev, ps.N, S["M"], S["hdims"], S["masks"]
+        E, main, trainable, wgrad, dgrad = ps.E, ps.main, ps.trainable, ps.wgrad, ps.dgrad
+        # ---- per-view adjoints of the x8 upsamples / gather of the stride-8 gradients
+        d_cam_low, d_rvd = [], []
+        for vw, (g_cam, g_cam_rv, g_fproj, g_rvd) in zip(S["views"], grads):
+            h, w, H, W = vw["h"], vw["w"], vw["H"], vw["W"]
+            if S["lowres"]:
+                d_cam_low.append(g_cam)
+                d_rvd.append(g_cam_rv)
+                continue
+            dc = None
+            if g_cam is not None:
+                dc = torch.empty(N, 21, h, w, device=dev, dtype=torch.float32)
+                L.resize_planar_bwd(g_cam.contiguous().float(), dc, N * 21, h, w, H, W, True)
+            dr = None
+            if g_cam_rv is not None:
+                dr = torch.empty(N, 21, h, w, device=dev, dtype=torch.float32)
+                L.resize_planar_bwd(g_cam_rv.contiguous().float(), dr, N * 21, h, w, H, W, True)
+            if g_rvd is not None:
+                dr = g_rvd.contiguous().float() if dr is None else dr + g_rvd
+            d_cam_low.append(dc)
+            d_rvd.append(dr)
+        # ---- PCM branch -> f9, f8_3, f8_4.  It ends in WEIGHT gradients only (f8_3 / f8_4 read conv4 / conv5 detached, resnet38_contrast.py:63-64),
+        # so nothing of the backbone's backward pass waits for it: it runs on its own stream beside the first blocks (0.5 ms of small kernels + two PCM
+        # launches that otherwise sit in front of the head's data gradient), joined before the gradients are consumed
+        # (same-box A/B against running it in line: 35.25 / 35.16 -> 34.94 / 34.94 ms per step; the b7 launches it overlaps slow down by ~1 %).
+        pcm_stream = None
+        if any(d is not None for d in d_rvd):
+            pcm_stream = self.stream("pcm", dev)
+            pcm_stream.wait_stream(main)
+            with torch.cuda.stream(pcm_stream):
+                DN = torch.empty(M, 32, device=dev, dtype=torch.float32)
+                dFh = torch.zeros(M, 192, device=dev, dtype=torch.float32)
+                DNb = torch.empty(M, 32, device=dev, dtype=torch.bfloat16) if S["Fb"] is not None else None
+                DNl = torch.empty(M, 32, device=dev, dtype=torch.bfloat16) if S["Fb"] is not None else None
+                for vw, dr in zip(S["views"], d_rvd):
+                    if dr is None:
+                        continue
                     off, hw = vw["off"], vw["h"] * vw["w"]
-                    gf = g[2].contiguous().float() if g[2] is not None else None
-                    L.head_grad_rows(gf, dc.contiguous() if dc is not None else None, S["head"][off:], d_head_rows[off:], HEAD_LD, N, hw)
-            chead = head_conv("head", 4096, HEAD_LD)
-            if trainable("fc_proj") or trainable("fc8"):          # fc_proj and fc8 are adjacent in flat_g: one [149,4096] block
-                L.conv_wgrad(S["fea"], d_head_rows, self.grad_slice("fc_proj", 149 * 4096), OC_dw=149, dtype=_cdt(dt), **chead.wgrad_kw(N))
-            s7, _ = P["bn"]["bn7"]
-            D = E(M, 4096)
-            dgrad(chead, d_head_rows, D, epi=1, scale=s7, drop=masks["dropout7"] if masks else None, mask=S["fea"])
-        # ---- blocks, last to first trainable
+                    if S["Fb"] is not None:
+                        L.pcm_backward_bf16(S["Fb"][off:], S["Gb"][off:], S["Gl"][off:], dr.contiguous(), vw["rvd"], vw["den"], DN[off:], DNb[off:],
+                                            DNl[off:], dFh[off:], N, hw)
+                    else:
+                        L.pcm_backward(S["Fh"][off:], S["G"][off:], dr.contiguous(), vw["rvd"], vw["den"], DN[off:], dFh[off:], N, hw)
+                dF = E(M, 192)
+                L.l2norm_backward(S["Fm"], 192, dFh, S["nrm"], dF, 192, M)
+                # feature rows are [f8_3 64 | f8_4 128 | x_s 3 | pad], f9.weight's columns [x_s | f8_3 | f8_4]: the weight-gradient kernel rotates
+                # its dW columns by 3 and accumulates straight into the flat gradient buffer (no staging tensor, no slice adds)
+                wgrad(head_conv("f9", FEAT_LD, 192, hdims), S["feat"], dF, IC_dw=195, dw_rot=3)
+                if trainable("f8_3") or trainable("f8_4"):
+                    d_feat = E(M, FEAT_LD)
+                    dgrad(head_conv("f9", FEAT_LD, 192, hdims), dF, d_feat, epi=1, mask=S["feat"])
+                    wgrad(head_conv("f8_3", 512, 64, hdims), S["conv4"], d_feat, ld_dy=FEAT_LD)
+                    wgrad(head_conv("f8_4", 1024, 128, hdims), S["conv5"], d_feat.view(-1)[64:], ld_dy=FEAT_LD)
+        ps.side = pcm_stream
+        # ---- head
+        if d_head_rows is None:
+            if all(dc is None for dc in d_cam_low) and all(g[2] is None for g in grads):
+                return ps.end_backward()
+            d_head_rows = E(M, HEAD_LD)
+            for vw, dc, g in zip(S["views"], d_cam_low, grads):
+                off, hw = vw["off"], vw["h"] * vw["w"]
+                gf = g[2].contiguous().float() if g[2] is not None else None
+                L.head_grad_rows(gf, dc.contiguous() if dc is not None else None, S["head"][off:], d_head_rows[off:], HEAD_LD, N, hw)
+        chead = head_conv("head", 4096, HEAD_LD, hdims)
+        if trainable("fc_proj") or trainable("fc8"):          # fc_proj and fc8 are adjacent in flat_g: one [149,4096] block
+            L.conv_wgrad(S["fea"], d_head_rows, self.grad_slice("fc_proj", 149 * 4096), OC_dw=149, dtype=_cdt(dt), **chead.wgrad_kw(N))
+        s7, _ = P["bn"]["bn7"]
+        taps = {"conv6": E(M, 4096)}
+        dgrad(chead, d_head_rows, taps["conv6"], epi=1, scale=s7, drop=masks["dropout7"] if masks else None, mask=S["fea"])
+        self._trunk_backward(ps, S, taps)                    # (from THIS frame: the PCM branch's operands above live until its stream is joined)
+        ps.end_backward()
+
+    def _trunk_backward(self, ps, S, taps):
+        """The trunk's backward pass, the block loop from the last block to the first trainable one.  taps {"conv6": D [M, 4096], the gradient at
+        conv6 before bn7; block: a gradient w.r.t. that block's input t (run_trunk_backward)}.  D is taken OUT of the dict, so that a caller
+        who keeps no other reference (run_backward: 0.44 GB at the training shape) has it freed when b7 has consumed it, as every later Din is."""
+        P, masks, D = ps.P, S["masks"], taps.pop("conv6")
+        E, rows_of, wgrad, dgrad, block_done = ps.E, ps.rows_of, ps.wgrad, ps.dgrad, ps.block_done
         for i in range(len(arch.BLOCKS) - 1, -1, -1):
             b = arch.BLOCKS[i]
             name, kind, cin, mid, cout, stride, fd, d, p = b
@@ -1000,17 +1000,15 @@ class Engine:
                 break
             same = arch.block_same_shape(b)
             din, dout = S["dims"][name]
-            Mi = rows_of(din)
-            Mo = rows_of(dout)
+            Mi, Mo = rows_of(din), rows_of(dout)
             sv = S[name]
             sa, _ = P["bn"][name + ".bn_branch2a"]
             first_trainable = name == "b3"               # its input comes from the frozen prefix
-            c1 = Conv(name + ".conv_branch1", cin, cout, 1, stride, 1, din, dout)
+            cv = block_launch_convs(b, din, dout)
+            c2a, c2b1, c1 = cv["branch2a"], cv["branch2b1"], cv.get("branch1")
             tap = taps.get(name)                         # a gradient w.r.t. this block's input t from outside the trunk: r_pre of the launch that writes Din (or tmp)
             if kind == "res":
                 s1, _ = P["bn"][name + ".bn_branch2b1"]
-                c2a = Conv(name + ".conv_branch2a", cin, mid, 3, stride, fd, din, dout)
-                c2b1 = Conv(name + ".conv_branch2b1", mid, cout, 3, 1, d, dout, dout)
                 du = E(Mo, mid)
                 # (each data gradient takes the weight gradient of the same dY into its launch: wseg_conv_bwd_pair)
                 dgrad(c2b1, D, du, epi=1, scale=s1, mask=sv["v"], pair=(c2b1, sv["v"], D))
@@ -1025,7 +1023,7 @@ class Engine:
                 Din = E(Mi, cin)
                 if same:
                     dgrad(c2a, du, Din, epi=1, scale=sa, mask=sv["t"], r_post=D, pair=(c2a, sv["t"], du))
-                elif fused_skip:                               # both data gradients into t: 9 taps of du + one K segment of D (+ the skip conv's weight gradient: same D)
+                elif fused_skip:                               # branch2a's and branch1's data gradients into t in one launch: 9 taps of du + one K segment of D (+ the skip conv's weight gradient: same D)
                     dgrad(c2a._replace(name=name + ".skip_fused"), du, Din, in2=D, IC2=cout, epi=1, scale=sa, mask=sv["t"], pair=(c1, sv["t"], D),
                           r_pre=tap)
                 else:
@@ -1040,17 +1038,15 @@ class Engine:
                 s2, _ = P["bn"][name + ".bn_branch2b2"]
                 d1 = masks[name + ".dropout_2b1"] if masks else None
                 d2 = masks[name + ".dropout_2b2"] if masks else None
-                c2a = Conv(name + ".conv_branch2a", cin, c4, 1, stride, 1, din, dout)
-                c2b1 = Conv(name + ".conv_branch2b1", c4, c2, 3, 1, d, dout, dout)
-                c2b2 = Conv(name + ".conv_branch2b2", c2, cout, 1, 1, 1, dout, dout)
+                c2b2 = cv["branch2b2"]
                 du2 = E(Mo, c2)
                 dgrad(c2b2, D, du2, epi=1, scale=s2, drop=d2, mask=sv["v2"], pair=(c2b2, sv["v2"], D))
                 du1 = E(Mo, c4)
                 dgrad(c2b1, du2, du1, epi=1, scale=s1, drop=d1, mask=sv["v1"], pair=(c2b1, sv["v1"], du2))
                 wgrad(c2a, sv["t"], du1)
                 Din = E(Mi, cin)
-                if (name + ".skip_fused") in P["wt"]:          # both 1x1 data gradients into t as ONE two-source product (+ the skip conv's weight gradient)
-                    dgrad(Conv(name + ".skip_fused", cin, cout, 1, 1, 1, din, dout), D, Din, epi=1, scale=sa, mask=sv["t"], in2=du1, IC2=c4,
+                if (name + ".skip_fused") in P["wt"]:          # branch1's and branch2a's 1x1 data gradients into t as ONE two-source product (+ the skip conv's weight gradient)
+                    dgrad(c1._replace(name=name + ".skip_fused"), D, Din, epi=1, scale=sa, mask=sv["t"], in2=du1, IC2=c4,
                           pair=(c1, sv["t"], D), r_pre=tap)
                 else:
                     tmp = E(Mi, cin)
@@ -1058,9 +1054,6 @@ class Engine:
                     dgrad(c2a, du1, Din, epi=1, scale=sa, mask=sv["t"], r_pre=tmp)
                 D = Din
                 block_done(name)
-        planes.clear()
-        if pcm_join[0] is not None:
-            main.wait_stream(pcm_join[0])
 
 
 class _NetFunction(torch.autograd.Function):
