@@ -501,6 +501,12 @@ if lib.wseg_sizeof_aff_label_desc() != C.sizeof(AffLabelDesc):
     raise ImportError(f"wseg_aff_label_desc: library {lib.wseg_sizeof_aff_label_desc()} bytes, binding {C.sizeof(AffLabelDesc)}: rebuild libwseg_hip.so")
 
 
+def augment_batch(descs_dev, n, max_pixels, lut, crop, lum_sums):
+    """descs_dev: address of n wseg_aug_desc on the device (augment.AugDesc: resize src -> tmp -> img, colour ops on img, finish into out);
+    max_pixels: the largest H * rw or rh * rw of the batch; lum_sums: scratch of 4 * n 64-bit words."""
+    _call("wseg_augment_batch", _v(descs_dev), n, max_pixels, _v(lut), crop, _v(lum_sums))
+
+
 def aff_augment_batch(descs_dev, n, max_pixels, lut, crop, lum_sums):
     """descs_dev: address of n wseg_aug_desc on the device (rw = W, rh = H, img = the uploaded image, jittered in place)."""
     _call("wseg_aff_augment_batch", _v(descs_dev), n, max_pixels, _v(lut), crop, _v(lum_sums))

@@ -201,8 +201,7 @@ class DeviceAugment:
         ev.record()
         self._slot = (self._slot + 1) % 4
         sums = torch.empty(n * 4, device=dev, dtype=torch.int64)
-        L.check(L.lib.wseg_augment_batch(C.c_void_p(d_desc.data_ptr()), n, max_pixels, C.c_void_p(self.lut.data_ptr()), crop,
-                                         C.c_void_p(sums.data_ptr()), C.c_void_p(L.stream_ptr())), "wseg_augment_batch")
+        L.augment_batch(d_desc, n, max_pixels, self.lut, crop, sums)
         self._keep = (d_img, d_tab, d_tmp, d_res, d_desc, sums)           # (alive until the next call: the kernels are asynchronous)
         return out, batch["label"].to(dev, non_blocking=True)
 

@@ -12,10 +12,14 @@
 //                        extrapolation clip; contrast needs the image's mean luminance (Convert.c rgb2l fixed point);
 //                        hue = Convert.c rgb2hsv / hsv2rgb with the float / double mix of that file, uint8 hue wrap
 //   finish               flip, 256-entry normalisation table per channel, crop / zero-pad placement, CHW f32
-// Every stage reproduces the host pipeline of wseg_amd/data.py BIT FOR BIT (tests/test_gpu_augment.py); the reference's own
-// torchvision transforms are not importable offline, so parity with them stays unpinned.
+// Every stage reproduces the host pipeline of wseg_amd/data.py BIT FOR BIT (the chain: tests/test_gpu_augment.py; stage by stage
+// against Pillow: tests/test_gpu_augment_kernels.py); the reference's own torchvision transforms are not importable offline, so
+// parity with them stays unpinned.
 #include <algorithm>
 #include "common.h"
+
+// Pillow rounds after every operation.  No multiply of this file may be fused with the add or subtract that follows it (see blend_u8).
+#pragma clang fp contract(off)
 
 namespace {
 
@@ -65,9 +69,14 @@ __global__ void aug_lum_sum_kernel(const wseg_aug_desc* __restrict__ descs, int 
 }
 
 // Blend.c: out = degenerate + alpha * (image - degenerate) in C float arithmetic (separate multiply and add), truncated;
-// outside [0, 1] the result is clipped to [0, 255] first
+// outside [0, 1] the result is clipped to [0, 255] first.  The product must be rounded to float before the sum.  hipcc contracts a
+// multiply and an add into one fused multiply-add by default, and __fmul_rn / __fadd_rn do not prevent it (the HIP headers define them
+// as plain `x * y` and `x + y`): contraction is switched off for this file (the pragma below the includes).  A fused blend differs
+// from Pillow at factors next to simple fractions (tests/test_gpu_augment_kernels.py: 4.4 million of the 2^24 colours at a
+// saturation factor of 1 - 2^-23); the same pragma keeps hsv2rgb's `x * y + 0.5` of its rounding in two steps.
 __device__ __forceinline__ unsigned char blend_u8(int deg, int img, float alpha) {
-  const float t = __fadd_rn((float)deg, __fmul_rn(alpha, (float)(img - deg)));
+  const float prod = alpha * (float)(img - deg);
+  const float t = (float)deg + prod;
   if (alpha >= 0.f && alpha <= 1.f) return (unsigned char)(int)t;
   if (t <= 0.f) return 0;
   if (t >= 255.f) return 255;
