@@ -10,7 +10,6 @@ files, draws the parameters from Python's `random` in the host chain's order and
 `DeviceAffData` does the rest on the GPU (csrc/augment.hip wseg_aff_augment_batch, csrc/aff_data.hip wseg_aff_labels_batch): the image bit
 for bit what the host chain gives from the same draws, the label map the dense rule's (tests/test_gpu_aff_data.py).
 """
-import ctypes as C
 import os
 import random
 
@@ -21,7 +20,8 @@ from torch.utils.data import Dataset
 
 from . import _lib as L
 from . import data as wdata
-from .augment import AugDesc
+from .augment import CROP_KEYS, AugDesc, fill_shared
+from .stage_io import DescRing
 
 MAX_PLANES = 21
 
@@ -143,7 +143,7 @@ def dense_bytes(batch):
 
 class DeviceAffData:
     """__call__(batch) -> (img float32 [N, 3, crop, crop], label uint8 [N, crop/8, crop/8]) on `device`, enqueued on the current stream;
-    nothing waits for the device (the descriptors go through a ring of page-locked staging buffers, as in augment.DeviceAugment).
+    nothing waits for the device (the descriptors go through stage_io.DescRing).
     Limits: crop % 8 == 0; at most 21 planes per stack; any H, W >= 1."""
 
     def __init__(self, device, crop=448):
@@ -153,8 +153,7 @@ class DeviceAffData:
         if self.crop < 8 or self.crop % 8:
             raise ValueError(f"DeviceAffData: crop {crop} is no positive multiple of 8 (the label map is crop/8 x crop/8)")
         self.lut = torch.from_numpy(normalize_lut_f32()).to(self.device).contiguous()
-        self._ring, self._slot = [], 0                       # page-locked descriptor staging: a pageable copy would make the host wait for the
-                                                             # stream (= the whole previous training step) on every call
+        self.ring = DescRing(self.device)
 
     def _check(self, p, n_img, n_planes, n_ids):
         """every offset and extent the kernels will follow, against the blobs (raw pointers beyond __call__)"""
@@ -185,9 +184,7 @@ class DeviceAffData:
             raise ValueError(f"DeviceAffData: plane ids outside [0, {MAX_PLANES})")
         for p in params:
             self._check(p, batch["img"].numel(), batch["planes"].numel(), ids_host.numel())
-        # (a DataLoader with pin_memory=True hands over page-locked blobs: its pinning thread did the copy in the background)
-        d_img, d_planes, d_ids = ((batch[k] if batch[k].is_pinned() else batch[k].pin_memory()).to(dev, non_blocking=True)
-                                  for k in ("img", "planes", "ids"))
+        d_img, d_planes, d_ids = (self.ring.to_device(batch[k]) for k in ("img", "planes", "ids"))
         img = torch.empty(n, 3, crop, crop, device=dev, dtype=torch.float32)
         label = torch.empty(n, crop // 8, crop // 8, device=dev, dtype=torch.uint8)
         aug, lab = (AugDesc * n)(), (L.AffLabelDesc * n)()
@@ -195,32 +192,15 @@ class DeviceAffData:
         for i, p in enumerate(params):
             a, b = aug[i], lab[i]
             a.H, a.W, a.rh, a.rw = p["H"], p["W"], p["H"], p["W"]
-            a.img, a.flip, a.hue_shift = d_img.data_ptr() + p["img_off"], p["flip"], p["hue_shift"]      # jittered in place: the upload is scratch
-            for j in range(4):
-                a.op[j], a.factor[j] = p["op"][j], p["factor"][j]
-            a.cont_top, a.cont_left, a.img_top, a.img_left, a.ch, a.cw = (p[k] for k in ("cont_top", "cont_left", "img_top", "img_left", "ch", "cw"))
-            a.out = img[i].data_ptr()
+            a.img, a.out = d_img.data_ptr() + p["img_off"], img[i].data_ptr()      # jittered in place: the upload is scratch
+            fill_shared(a, p)
             for s in range(2):
                 b.planes[s], b.ids[s], b.np[s] = d_planes.data_ptr() + 4 * p["planes_off"][s], d_ids.data_ptr() + 4 * p["ids_off"][s], p["np"][s]
             b.H, b.W, b.plane_stride, b.flip = p["H"], p["W"], p["plane_stride"], p["flip"]
-            b.cont_top, b.cont_left, b.img_top, b.img_left, b.ch, b.cw = (p[k] for k in ("cont_top", "cont_left", "img_top", "img_left", "ch", "cw"))
+            for k in CROP_KEYS:
+                setattr(b, k, p[k])
             max_pixels = max(max_pixels, p["H"] * p["W"])
-        lab_at = (C.sizeof(aug) + 15) // 16 * 16               # both descriptor arrays in one staging buffer, one copy
-        nbytes = lab_at + C.sizeof(lab)
-        if len(self._ring) < 4 or self._ring[self._slot][0].numel() < nbytes:
-            entry = (torch.empty(max(nbytes, 64 * (C.sizeof(AugDesc) + C.sizeof(L.AffLabelDesc))), dtype=torch.uint8).pin_memory(), torch.cuda.Event())
-            if len(self._ring) < 4:
-                self._ring.append(entry); self._slot = len(self._ring) - 1
-            else:
-                self._ring[self._slot] = entry
-        else:
-            self._ring[self._slot][1].synchronize()           # the copy that last used this slot has been consumed
-        stage, ev = self._ring[self._slot]
-        C.memmove(stage.data_ptr(), C.addressof(aug), C.sizeof(aug))
-        C.memmove(stage.data_ptr() + lab_at, C.addressof(lab), C.sizeof(lab))
-        d_desc = stage[:nbytes].to(dev, non_blocking=True)
-        ev.record()
-        self._slot = (self._slot + 1) % 4
+        d_desc, (_, lab_at) = self.ring.upload(aug, lab)        # both descriptor arrays in one staging buffer, one copy
         sums = torch.empty(n * 4, device=dev, dtype=torch.int64)
         self._keep = (d_img, d_planes, d_ids, d_desc, sums)   # (alive until the next call: the kernels are asynchronous)
         self._last = (d_desc.data_ptr(), lab_at, n, max_pixels, sums, img, label)

@@ -7,7 +7,6 @@ times (dense GEMMs) and multiplies the pooled CAM by it.  Here the same product 
 ignored, as in the reference (its bg score is a hard-coded 0.27 and its CRF block is commented out).
 """
 import argparse
-import importlib
 import os
 
 import numpy as np
@@ -19,6 +18,7 @@ from . import data as wdata
 from . import synth
 from .eval import DeviceEval, load_gt
 from .safe_npy import load_pickled_npy
+from .stage_io import WriteBehind, cam_planes, load_net
 
 BG_SCORE = 0.27
 
@@ -44,20 +44,9 @@ def random_walk_image(model, img, cam_dict, orig_size, beta=8, logt=6, return_ca
     wgt = torch.empty(1, 2 * P, area, device=dev, dtype=torch.float32)
     rsum = torch.empty(1, area, device=dev, dtype=torch.float32)
     L.rw_prepare(aff, wgt, rsum, 1, h, w, r, beta)
-    src = [-1] * 21
-    cams = None
-    if cam_dict:
-        keys = sorted(cam_dict)
-        for i, k in enumerate(keys):
-            if not 0 <= int(k) < 20:
-                raise ValueError(f"CAM class {k} outside 0..19")
-            src[int(k) + 1] = i
-        cams = torch.stack([torch.as_tensor(np.asarray(cam_dict[k], np.float32)) if not torch.is_tensor(cam_dict[k]) else cam_dict[k].float()
-                            for k in keys])
-        assert tuple(cams.shape[1:]) == (H, W), (tuple(cams.shape), orig_size)
-        cams = cams.to(dev, non_blocking=True).contiguous()
+    cams, idx, _ = cam_planes(cam_dict, (H, W), dev)
     pooled = torch.empty(21, dh, dw, device=dev, dtype=torch.float32)
-    L.rw_pool(cams, src, BG_SCORE, pooled, H, W, dh, dw)
+    L.rw_pool(cams, [-1] + idx, BG_SCORE, pooled, H, W, dh, dw)
     cam_rw = torch.empty_like(pooled)
     L.random_walk(wgt, rsum, pooled, cam_rw, 1, 21, h, w, r, logt)
     pred = torch.empty(H, W, device=dev, dtype=torch.uint8)
@@ -86,48 +75,27 @@ def build_parser():
 def main(argv=None):
     args = build_parser().parse_args(argv)
     os.makedirs(args.out_rw, exist_ok=True)
-    Net = getattr(importlib.import_module(args.network), 'Net')
-    model = Net(precision=args.precision) if args.precision else Net()
-    if args.weights == "procedural":
-        model.load_state_dict(synth.procedural_aff_state_dict(0))
-    else:
-        model.load_state_dict(torch.load(args.weights, map_location="cpu", weights_only=True))
+    model = load_net(args.network, args.weights, args.precision, synth.procedural_aff_state_dict)
     model.eval()
     model.cuda()
 
     ds = wdata.VOC12ImageDataset(args.infer_list, args.voc12_root, transform=[np.asarray, model.normalize, wdata.HWC_to_CHW])
     loader = torch.utils.data.DataLoader(ds, shuffle=False, num_workers=args.num_workers, pin_memory=True)
 
-    # One image behind, as contrast_infer.main: the mask of image i starts its way to a pinned host buffer, and only then is the png of
-    # image i - 1 written, so the file write and the loader hand-over overlap the GPU.
-    def start(name, pred):
-        host = torch.empty(pred.shape, dtype=pred.dtype, pin_memory=True)
-        host.copy_(pred, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return name, host, ev
-
-    def finish(item):
-        name, host, ev = item
-        ev.synchronize()
+    def write(name, host):
         PIL.Image.fromarray(host.numpy()).save(os.path.join(args.out_rw, name + '.png'))
 
     ev = DeviceEval("cuda") if args.gt_dir is not None else None       # --gt_dir: confusion counts of every mask, on the device until the end
-    pending = None
-    for name, img in loader:
-        name = name[0]
-        H, W = img.shape[2], img.shape[3]
-        cam = load_pickled_npy(os.path.join(args.cam_dir, name + '.npy'))
-        gt = load_gt(args.gt_dir, name, (H, W)) if ev is not None else None
-        pred = random_walk_image(model, img, cam, (H, W), args.beta, args.logt)
-        if gt is not None:
-            ev.add_masks(pred, torch.from_numpy(gt).pin_memory().to(pred.device, non_blocking=True))
-        item = start(name, pred)
-        if pending is not None:
-            finish(pending)
-        pending = item
-    if pending is not None:
-        finish(pending)
+    with WriteBehind(write) as out:                 # the png of image i - 1 is written while image i computes
+        for name, img in loader:
+            name = name[0]
+            H, W = img.shape[2], img.shape[3]
+            cam = load_pickled_npy(os.path.join(args.cam_dir, name + '.npy'))
+            gt = load_gt(args.gt_dir, name, (H, W)) if ev is not None else None
+            pred = random_walk_image(model, img, cam, (H, W), args.beta, args.logt)
+            if gt is not None:
+                ev.add_masks(pred, torch.from_numpy(gt).pin_memory().to(pred.device, non_blocking=True))
+            out.submit(name, pred)
     if ev is None:
         return None
     res = ev.mask_result()

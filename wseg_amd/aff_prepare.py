@@ -18,6 +18,7 @@ import torch
 from . import data as wdata
 from .crf import crf_inference, labels_from_cams
 from .safe_npy import load_pickled_npy
+from .stage_io import WriteBehind
 
 CRF_BILATERAL, CRF_GAUSSIAN, CRF_T = (80, 13, 10), (3, 3), 10          # aff_prepare.py:39-47, :34
 
@@ -48,7 +49,7 @@ class _Images(torch.utils.data.Dataset):
         with PIL.Image.open(wdata.get_img_path(name, self.root)) as im:
             img = torch.from_numpy(np.array(im.convert("RGB")))
         cams = load_pickled_npy(os.path.join(self.cam_dir, name + '.npy'))
-        return name, img, {int(k): torch.from_numpy(np.asarray(v, np.float32)) for k, v in cams.items()}
+        return name, img, {k: torch.from_numpy(np.asarray(v, np.float32)) for k, v in cams.items()}      # (keys as read: cam_planes judges them)
 
 
 def main(argv=None):
@@ -64,32 +65,15 @@ def main(argv=None):
                                          pin_memory=True, batch_size=None)
     dev = torch.device("cuda")
 
-    # One image behind, as contrast_infer.main: Q of image i starts its way to a pinned host buffer, and only then are the files of
-    # image i - 1 written.
-    def start(name, Q):
-        host = torch.empty(Q.shape, dtype=Q.dtype, pin_memory=True)
-        host.copy_(Q, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return name, host, ev
-
-    def finish(item):
-        name, host, ev = item
-        ev.synchronize()
+    def write(name, host):
         for s, d in enumerate(folders):
             np.save(os.path.join(d, name + '.npy'), host[s].numpy())
 
-    pending = None
-    for name, img, cams in loader:
-        img = img.to(dev, non_blocking=True)
-        labels = labels_from_cams(cams, alpha=alphas, size=tuple(img.shape[:2]), device=dev)
-        Q = crf_inference(img, labels, t=CRF_T, bilateral=CRF_BILATERAL, gaussian=CRF_GAUSSIAN)
-        item = start(name, Q)
-        if pending is not None:
-            finish(pending)
-        pending = item
-    if pending is not None:
-        finish(pending)
+    with WriteBehind(write) as out:                 # the files of image i - 1 are written while image i computes
+        for name, img, cams in loader:
+            img = img.to(dev, non_blocking=True)
+            labels = labels_from_cams(cams, alpha=alphas, size=tuple(img.shape[:2]), device=dev)
+            out.submit(name, crf_inference(img, labels, t=CRF_T, bilateral=CRF_BILATERAL, gaussian=CRF_GAUSSIAN))
 
 
 if __name__ == '__main__':

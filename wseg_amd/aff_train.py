@@ -13,7 +13,6 @@ reference's own three loss lines as torch ops — computes the same step (tests/
 data-parallel exchange of the contrast trainer is not wired to this step.
 """
 import argparse
-import importlib
 import os
 import random
 import time
@@ -24,7 +23,8 @@ import torch
 from . import aff_loss
 from . import synth
 from .engine import AFF_FEAT_C
-from .optim import PolyOptimizer
+from .optim import build_optimizer            # (tests and scripts import it from here)
+from .stage_io import load_net
 
 KEYS = aff_loss.STATS
 LOG_EVERY = 50
@@ -33,17 +33,6 @@ LOG_EVERY = 50
 def max_step_of(n_images, batch_size, max_epoches):
     """aff_train.py:70"""
     return n_images // batch_size * max_epoches
-
-
-def build_optimizer(model, lr, wt_dec, max_step):
-    """aff_train.py:72-78: lr, 2 lr, 10 lr, 20 lr; weight decay on groups 0 and 2."""
-    param_groups = model.get_parameter_groups()
-    return PolyOptimizer([
-        {'params': param_groups[0], 'lr': lr, 'weight_decay': wt_dec},
-        {'params': param_groups[1], 'lr': 2 * lr, 'weight_decay': 0},
-        {'params': param_groups[2], 'lr': 10 * lr, 'weight_decay': wt_dec},
-        {'params': param_groups[3], 'lr': 20 * lr, 'weight_decay': 0}
-    ], lr=lr, weight_decay=wt_dec, max_step=max_step)
 
 
 class AffTrainer:
@@ -94,27 +83,15 @@ def main(argv=None):
     os.makedirs(os.path.join('result', args.session_name), exist_ok=True)
     print(vars(args))
 
-    Net = getattr(importlib.import_module(args.network), 'Net')
-    model = Net(precision=args.precision) if args.precision else Net()
-
     ds = aff_data.VOC12AffDatasetRaw(args.train_list, args.la_crf_dir, args.ha_crf_dir, args.voc12_root, args.crop_size)
     loader = torch.utils.data.DataLoader(ds, batch_size=args.batch_size, shuffle=True, num_workers=args.num_workers, pin_memory=True,
                                          drop_last=True, collate_fn=aff_data.aff_collate,
                                          worker_init_fn=lambda wid: (np.random.seed(1 + wid), random.seed(1 + wid)))
     to_device = aff_data.DeviceAffData(dev, args.crop_size)
     max_step = max_step_of(len(ds), args.batch_size, args.max_epoches)
+    model = load_net(args.network, args.weights, args.precision, synth.procedural_aff_state_dict, strict=False, warn_mismatch=True)
     optimizer = build_optimizer(model, args.lr, args.wt_dec, max_step)
 
-    if args.weights == "procedural":
-        weights_dict = synth.procedural_aff_state_dict(0)
-    elif args.weights[-7:] == '.params':
-        raise SystemExit("mxnet .params conversion needs mxnet (absent offline): convert to a .pth state_dict first")
-    else:
-        weights_dict = torch.load(args.weights, map_location="cpu", weights_only=True)
-    try:                                                    # (aff_train.py:88-92: a size mismatch is a warning there)
-        model.load_state_dict(weights_dict, strict=False)
-    except RuntimeError as e:
-        print(e)
     model.cuda(dev)
     model.train()
     trainer = AffTrainer(model, optimizer)

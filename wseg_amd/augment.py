@@ -19,6 +19,7 @@ from torch.utils.data import Dataset
 
 from . import _lib as L
 from . import data as wdata
+from .stage_io import DescRing
 
 PRECISION_BITS = 32 - 8 - 2          # Pillow Resample.c
 
@@ -140,6 +141,18 @@ if L.lib.wseg_sizeof_aug_desc() != C.sizeof(AugDesc):
     raise ImportError(f"wseg_aug_desc: library {L.lib.wseg_sizeof_aug_desc()} bytes, binding {C.sizeof(AugDesc)}: rebuild libwseg_hip.so")
 
 
+CROP_KEYS = ("cont_top", "cont_left", "img_top", "img_left", "ch", "cw")
+
+
+def fill_shared(d, p):
+    """the AugDesc fields every chain fills from its draws: the flip bit, the four colour ops in their drawn order, the crop window"""
+    d.flip, d.hue_shift = p["flip"], p["hue_shift"]
+    for j in range(4):
+        d.op[j], d.factor[j] = p["op"][j], p["factor"][j]
+    for k in CROP_KEYS:
+        setattr(d, k, p[k])
+
+
 def normalize_lut(mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
     """float32((v / 255. - mean) / std) for v = 0..255 per channel — the values network/resnet38d.py:104-118 produces (float64 arithmetic,
     stored to float32)."""
@@ -151,8 +164,7 @@ class DeviceAugment:
     def __init__(self, device, crop=448):
         self.device, self.crop = torch.device(device), crop
         self.lut = torch.from_numpy(normalize_lut()).to(self.device).contiguous()
-        self._ring, self._slot = [], 0                       # page-locked descriptor staging: a pageable copy would make the host wait for the
-                                                             # stream (= the whole previous training step) on every call
+        self.ring = DescRing(self.device)
 
     def __call__(self, batch):
         """batch: what `collate` made of a list of samples (a list of samples is accepted too) -> (float32 [N, 3, crop, crop] on the
@@ -163,9 +175,7 @@ class DeviceAugment:
             batch = collate(batch)
         params, crop, dev = batch["params"], self.crop, self.device
         n = len(params)
-        # (a DataLoader with pin_memory=True hands over page-locked blobs: its pinning thread did the copy in the background)
-        d_img = (batch["img"] if batch["img"].is_pinned() else batch["img"].pin_memory()).to(dev, non_blocking=True)
-        d_tab = (batch["tab"] if batch["tab"].is_pinned() else batch["tab"].pin_memory()).to(dev, non_blocking=True)
+        d_img, d_tab = self.ring.to_device(batch["img"]), self.ring.to_device(batch["tab"])
         tmp_off, res_off, total_tmp, total_res = [], [], 0, 0
         for p in params:
             tmp_off.append(total_tmp); total_tmp += (p["H"] * p["rw"] * 3 + 15) // 16 * 16
@@ -180,26 +190,10 @@ class DeviceAugment:
             d.src, d.H, d.W, d.rh, d.rw = d_img.data_ptr() + p["img_off"], p["H"], p["W"], p["rh"], p["rw"]
             d.xb, d.xk, d.xks = d_tab.data_ptr() + 4 * to[0], d_tab.data_ptr() + 4 * to[1], p["xks"]
             d.yb, d.yk, d.yks = d_tab.data_ptr() + 4 * to[2], d_tab.data_ptr() + 4 * to[3], p["yks"]
-            d.tmp, d.img, d.flip, d.hue_shift = d_tmp.data_ptr() + mo, d_res.data_ptr() + ro, p["flip"], p["hue_shift"]
-            for j in range(4):
-                d.op[j], d.factor[j] = p["op"][j], p["factor"][j]
-            d.cont_top, d.cont_left, d.img_top, d.img_left, d.ch, d.cw = (p[k] for k in ("cont_top", "cont_left", "img_top", "img_left", "ch", "cw"))
-            d.out = out[i].data_ptr()
+            d.tmp, d.img, d.out = d_tmp.data_ptr() + mo, d_res.data_ptr() + ro, out[i].data_ptr()
+            fill_shared(d, p)
             max_pixels = max(max_pixels, p["H"] * p["rw"], p["rh"] * p["rw"])
-        nbytes = C.sizeof(descs)
-        if len(self._ring) < 4 or self._ring[self._slot][0].numel() < nbytes:
-            entry = (torch.empty(max(nbytes, 64 * C.sizeof(AugDesc)), dtype=torch.uint8).pin_memory(), torch.cuda.Event())
-            if len(self._ring) < 4:
-                self._ring.append(entry); self._slot = len(self._ring) - 1
-            else:
-                self._ring[self._slot] = entry
-        else:
-            self._ring[self._slot][1].synchronize()           # the copy that last used this slot has been consumed
-        stage, ev = self._ring[self._slot]
-        C.memmove(stage.data_ptr(), C.addressof(descs), nbytes)
-        d_desc = stage[:nbytes].to(dev, non_blocking=True)
-        ev.record()
-        self._slot = (self._slot + 1) % 4
+        d_desc, _ = self.ring.upload(descs)
         sums = torch.empty(n * 4, device=dev, dtype=torch.int64)
         L.augment_batch(d_desc, n, max_pixels, self.lut, crop, sums)
         self._keep = (d_img, d_tab, d_tmp, d_res, d_desc, sums)           # (alive until the next call: the kernels are asynchronous)

@@ -5,7 +5,6 @@ labels with a constant background score of 0.26, sxy 50 / srgb 5, 10 iterations.
 background score is the constant 0.26 whatever --out_cam_pred_alpha says, and --crf_iters is parsed and never used (t = 10).  The CRF is wseg_amd.crf: exact mean field on the device; agreement with pydensecrf's permutohedral
 approximation is unmeasured."""
 import argparse
-import importlib
 import os
 
 import numpy as np
@@ -17,6 +16,7 @@ from . import synth
 from .crf import crf_inference, labels_from_cams
 from .eval import DeviceEval, curve_lines, load_gt
 from .infer import infer_image
+from .stage_io import WriteBehind, load_net
 
 CRF_BG_SCORE, CRF_BILATERAL, CRF_GAUSSIAN, CRF_T = 0.26, (50, 5, 10), (3, 3), 10        # contrast_infer.py:104, 121-122, 113
 
@@ -50,42 +50,15 @@ def build_parser():
 def main(argv=None):
     args = build_parser().parse_args(argv)
 
-    Net = getattr(importlib.import_module(args.network), 'Net')
-    model = Net(precision=args.precision) if args.precision else Net()
-    if args.weights == "procedural":
-        model.load_state_dict(synth.procedural_state_dict(0))
-    else:
-        model.load_state_dict(torch.load(args.weights, map_location="cpu", weights_only=True))
+    model = load_net(args.network, args.weights, args.precision, synth.procedural_state_dict)
     model.eval()
     model.cuda()
 
     ds = wdata.VOC12ClsDatasetMSF(args.infer_list, args.voc12_root, args.labels, scales=[0.5, 1.0, 1.5, 2.0],
                                   inter_transform=[np.asarray, model.normalize, wdata.HWC_to_CHW])
     loader = torch.utils.data.DataLoader(ds, shuffle=False, num_workers=args.num_workers, pin_memory=True)
-    # One image behind: the device work of image i is enqueued (nothing in infer_image synchronises), its outputs start their way to pinned host
-    # buffers, and only then are the files of image i - 1 written — the png / npy writes and the loader hand-over overlap the GPU instead of
-    # alternating with it (the reference's loop, contrast_infer.py:52-99, syncs per image on `.cpu()`).
-    def start(img_name, pred, cam_dict, crf_pred):
-        host_pred = torch.empty(pred.shape, dtype=pred.dtype, pin_memory=True)
-        host_pred.copy_(pred, non_blocking=True)
-        host_crf = None
-        if crf_pred is not None:
-            host_crf = torch.empty(crf_pred.shape, dtype=crf_pred.dtype, pin_memory=True)
-            host_crf.copy_(crf_pred, non_blocking=True)
-        host_cams = None
-        if args.out_cam is not None:
-            host_cams = {}
-            for k, v in cam_dict.items():
-                h = torch.empty(v.shape, dtype=v.dtype, pin_memory=True)
-                h.copy_(v, non_blocking=True)
-                host_cams[k] = h
-        ev = torch.cuda.Event()
-        ev.record()
-        return img_name, host_pred, host_cams, host_crf, ev
-
-    def finish(item):
-        img_name, host_pred, host_cams, host_crf, ev = item
-        ev.synchronize()
+    def write(img_name, host):
+        host_pred, host_crf, host_cams = host
         if host_crf is not None:
             PIL.Image.fromarray(host_crf.numpy()).save(os.path.join(args.out_crf, img_name + '.png'))
         if host_cams is not None:
@@ -102,29 +75,26 @@ def main(argv=None):
     if args.gt_dir is not None:
         ev_curve, ev_pred = DeviceEval("cuda"), DeviceEval("cuda")
         ev_crf = DeviceEval("cuda") if args.out_crf is not None else None
-    pending = None
-    for it, (img_name, img_list, label) in enumerate(loader):
-        img_name, label = img_name[0], label[0]
-        with PIL.Image.open(wdata.get_img_path(img_name, args.voc12_root)) as im:      # (header only: the reference decodes the image again for its shape)
-            W, H = im.size
-            rgb = np.array(im.convert("RGB")) if args.out_crf is not None else None
-        gt = load_gt(args.gt_dir, img_name, (H, W)) if args.gt_dir is not None else None
-        norm_cam, pred, cam_dict = infer_image(model, img_list, label, (H, W), args.out_cam_pred_alpha)
-        crf_pred = None
-        if rgb is not None:
-            crf_pred = crf_prediction(torch.from_numpy(rgb).pin_memory().to(pred.device, non_blocking=True), cam_dict)
-        if gt is not None:
-            gt = torch.from_numpy(gt).pin_memory().to(pred.device, non_blocking=True)
-            ev_curve.add_cams(cam_dict, gt)
-            ev_pred.add_masks(pred, gt)
-            if crf_pred is not None:
-                ev_crf.add_masks(crf_pred, gt)
-        item = start(img_name, pred, cam_dict, crf_pred)
-        if pending is not None:
-            finish(pending)
-        pending = item
-    if pending is not None:
-        finish(pending)
+    # One image behind: the device work of image i is enqueued (nothing in infer_image synchronises) and only then are the files of
+    # image i - 1 written (the reference's loop, contrast_infer.py:52-99, syncs per image on `.cpu()`).
+    with WriteBehind(write) as out:
+        for it, (img_name, img_list, label) in enumerate(loader):
+            img_name, label = img_name[0], label[0]
+            with PIL.Image.open(wdata.get_img_path(img_name, args.voc12_root)) as im:      # (header only: the reference decodes the image again for its shape)
+                W, H = im.size
+                rgb = np.array(im.convert("RGB")) if args.out_crf is not None else None
+            gt = load_gt(args.gt_dir, img_name, (H, W)) if args.gt_dir is not None else None
+            norm_cam, pred, cam_dict = infer_image(model, img_list, label, (H, W), args.out_cam_pred_alpha)
+            crf_pred = None
+            if rgb is not None:
+                crf_pred = crf_prediction(torch.from_numpy(rgb).pin_memory().to(pred.device, non_blocking=True), cam_dict)
+            if gt is not None:
+                gt = torch.from_numpy(gt).pin_memory().to(pred.device, non_blocking=True)
+                ev_curve.add_cams(cam_dict, gt)
+                ev_pred.add_masks(pred, gt)
+                if crf_pred is not None:
+                    ev_crf.add_masks(crf_pred, gt)
+            out.submit(img_name, (pred, crf_pred, cam_dict if args.out_cam is not None else None))
     if ev_curve is None:
         return None
     mious = [r['mIoU'] for r in ev_curve.curve_results()]

@@ -11,7 +11,6 @@ decode the JPEGs and draw the random parameters), --seed (rank r seeds torch wit
 `imps` definition (images, not views, per second; :413-420); tensorboardX is not available offline.
 """
 import argparse
-import importlib
 import os
 import random
 import time
@@ -22,7 +21,8 @@ import torch.distributed as dist
 
 from . import data as wdata
 from . import synth
-from .optim import PolyOptimizer
+from .optim import build_optimizer
+from .stage_io import load_net
 from .train import Trainer
 
 KEYS = ['loss', 'loss_cls', 'loss_er', 'loss_ecr', 'loss_nce', 'loss_intra_nce', 'loss_cross_nce', 'loss_cross_nce2']
@@ -70,8 +70,7 @@ def main(argv=None):
     if rank == 0:
         print(vars(args))
 
-    Net = getattr(importlib.import_module(args.network), 'Net')
-    model = Net(precision=args.precision) if args.precision else Net()
+    model = load_net(args.network, args.weights, args.precision, synth.procedural_state_dict, strict=False, device=dev)
 
     aug = None
     if args.synthetic:
@@ -96,21 +95,7 @@ def main(argv=None):
     steps_per_epoch = n_img // args.batch_size
     max_step = steps_per_epoch * args.max_epoches
 
-    param_groups = model.get_parameter_groups()
-    optimizer = PolyOptimizer([
-        {'params': param_groups[0], 'lr': args.lr, 'weight_decay': args.wt_dec},
-        {'params': param_groups[1], 'lr': 2 * args.lr, 'weight_decay': 0},
-        {'params': param_groups[2], 'lr': 10 * args.lr, 'weight_decay': args.wt_dec},
-        {'params': param_groups[3], 'lr': 20 * args.lr, 'weight_decay': 0}
-    ], lr=args.lr, weight_decay=args.wt_dec, max_step=max_step)
-
-    if args.weights == "procedural":
-        weights_dict = synth.procedural_state_dict(0, device=dev)
-    elif args.weights[-7:] == '.params':
-        raise SystemExit("mxnet .params conversion needs mxnet (absent offline): convert to a .pth state_dict first")
-    else:
-        weights_dict = torch.load(args.weights, map_location="cpu", weights_only=True)
-    model.load_state_dict(weights_dict, strict=False)
+    optimizer = build_optimizer(model, args.lr, args.wt_dec, max_step)
     model.cuda(dev)
     model.train()
     trainer = Trainer(model, optimizer, args.bg_threshold, random.Random(args.seed * 1000003 + rank), args.rng_parity)

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .stage_io import cam_planes
 
 MAX_SETS_PER_PASS = L.CRF_MAX_COLUMNS // 21      # label sets of 21 labels that share one pass over the pairs
 
@@ -26,24 +27,6 @@ def bg_rule(bg_score=None, alpha=None):
     return L.CRF_BG_POWER, float(alpha)
 
 
-def _stack_cams(cam_dict, size, n_labels, device):
-    src = [-1] * n_labels
-    if not cam_dict:
-        if size is None:
-            raise ValueError("labels_from_cams: an empty CAM dictionary needs size=(H, W)")
-        return None, src, tuple(size)
-    keys = sorted(cam_dict)
-    for i, k in enumerate(keys):
-        if not 0 <= int(k) < n_labels - 1:
-            raise ValueError(f"CAM class {k} outside 0..{n_labels - 2}")
-        src[int(k) + 1] = i
-    planes = [cam_dict[k].float() if torch.is_tensor(cam_dict[k]) else torch.as_tensor(np.asarray(cam_dict[k], np.float32)) for k in keys]
-    cams = torch.stack(planes).to(device, non_blocking=True).contiguous()
-    if size is not None and tuple(cams.shape[1:]) != tuple(size):
-        raise ValueError(f"CAM planes are {tuple(cams.shape[1:])}, expected {tuple(size)}")
-    return cams, src, tuple(cams.shape[1:])
-
-
 @torch.no_grad()
 def labels_from_cams(cam_dict, bg_score=None, alpha=None, size=None, n_labels=21, device="cuda"):
     """cam_dict {class 0..19: float [H, W]} (numpy or torch, what contrast_infer writes) -> uint8 device labels: the arg-max over
@@ -54,7 +37,8 @@ def labels_from_cams(cam_dict, bg_score=None, alpha=None, size=None, n_labels=21
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("labels_from_cams runs on the device only (wseg_amd has no CPU fallback)")
-    cams, src, (H, W) = _stack_cams(cam_dict, size, n_labels, device)
+    cams, idx, (H, W) = cam_planes(cam_dict, size, device, n_labels - 1)
+    src = [-1] + idx
     out = torch.empty(len(rules), H, W, device=device, dtype=torch.uint8)
     with torch.cuda.device(device):
         for s, (rule, param) in enumerate(rules):

@@ -128,11 +128,12 @@ class DeviceEval:
             raise ValueError(f"num_cls={num_cls} outside 1..21")
         import torch
         from . import _lib as L
-        self._torch, self._L = torch, L
+        from .stage_io import cam_planes
+        self._torch, self._L, self._cam_planes = torch, L, cam_planes
         self.num_cls = num_cls
         self.conf = torch.zeros(GT_ROWS, GT_ROWS, dtype=torch.int64, device=device)
         self.hist = torch.zeros(GT_ROWS, FG_CLASSES, self.thr.size + 1, dtype=torch.int64, device=device)
-        self.device = self.hist.device               # with its index ("cuda" -> cuda:0), as tensors report it: _planes compares devices
+        self.device = self.hist.device               # with its index ("cuda" -> cuda:0), as tensors report it
 
     def _u8(self, x, what):
         torch = self._torch
@@ -148,24 +149,10 @@ class DeviceEval:
             raise ValueError(f"prediction {tuple(pred.shape)} against ground truth {tuple(gt.shape)}")
         self._L.eval_confusion(pred, gt, gt.numel(), self.conf)
 
-    def _planes(self, maps, n):
-        """(keep-alive tensor(s), base address, stride in elements, plane index of each map): views into one float32 device tensor
-        (what infer_image returns) are read in place, anything else is stacked and copied over."""
-        torch = self._torch
-        if all(torch.is_tensor(m) and m.device == self.device and m.dtype == torch.float32 and m.is_contiguous() for m in maps) \
-                and len({m.untyped_storage().data_ptr() for m in maps}) == 1:
-            ptrs = [m.data_ptr() for m in maps]
-            offs = [(p - min(ptrs)) // 4 for p in ptrs]
-            stride = n if all(o % n == 0 for o in offs) else int(np.gcd.reduce(offs))       # (planes of one [C, H, W] tensor: H*W apart)
-            if len(set(offs)) == len(offs) and stride >= n:
-                return maps, min(ptrs), stride, [o // stride for o in offs]
-        stack = torch.stack([m.detach().float() if torch.is_tensor(m) else torch.from_numpy(np.asarray(m, np.float32)) for m in maps])
-        stack = stack.to(self.device, non_blocking=True).contiguous()
-        return stack, stack.data_ptr(), n, list(range(len(maps)))
-
     def add_cams(self, cams, gt, classes=None):
         """cams: {class 0..19: [H, W]} (torch or numpy: infer_image's cam_dict, or what load_pickled_npy returns; empty = every score 0),
-        or a [K, H, W] array holding the planes of `classes` (default 0..K-1), which crosses to the device in one copy."""
+        or a [K, H, W] array holding the planes of `classes` (default 0..K-1), which crosses to the device in one copy.  Views into one
+        float32 device tensor are read in place (stage_io.cam_planes)."""
         torch = self._torch
         gt = self._u8(gt, "gt")
         n = gt.numel()
@@ -174,18 +161,13 @@ class DeviceEval:
                 cams = torch.from_numpy(np.ascontiguousarray(cams, np.float32))
             cams = cams.to(self.device, non_blocking=True)
             cams = {int(c): cams[i] for i, c in enumerate(range(len(cams)) if classes is None else classes)}
-        keys = sorted(cams)
-        if any(int(k) != k or not 0 <= int(k) < FG_CLASSES for k in keys):
-            raise ValueError(f"CAM classes {keys} outside 0..{FG_CLASSES - 1}")
-        if n == 0 or any(tuple(cams[k].shape) != tuple(gt.shape) for k in keys):
-            raise ValueError(f"CAM maps {[tuple(cams[k].shape) for k in keys]} against ground truth {tuple(gt.shape)}")
-        src, keep, base, stride, nplanes = [-1] * FG_CLASSES, None, None, 0, 0
-        if keys:
-            keep, base, stride, idx = self._planes([cams[k] for k in keys], n)        # (keep: the planes stay referenced until the launch is enqueued)
-            nplanes = max(idx) + 1
-            for k, i in zip(keys, idx):
-                src[int(k)] = i
-        self._L.eval_curve(base, stride, nplanes, src, gt, n, self.thr, self.hist)
+        if n == 0:
+            raise ValueError(f"ground truth {tuple(gt.shape)} is empty")
+        planes, idx, _ = self._cam_planes(cams, gt.shape, self.device, FG_CLASSES)      # (planes stays referenced until the launch is enqueued)
+        if planes is None:
+            self._L.eval_curve(None, 0, 0, idx, gt, n, self.thr, self.hist)
+        else:
+            self._L.eval_curve(planes.data_ptr(), n, planes.shape[0], idx, gt, n, self.thr, self.hist)
 
     def counts(self, which):
         """int64 (P, T, TP): 'mask' -> [num_cls] each, 'curve' -> [thresholds, num_cls] each.  Reads the counters (synchronises)."""

@@ -105,3 +105,14 @@ class PolyOptimizer(torch.optim.SGD):
                         p.grad = None
                     else:
                         p.grad.zero_()
+
+
+def build_optimizer(model, lr, wt_dec, max_step):
+    """contrast_train.py:92-98 / aff_train.py:72-78: lr, 2 lr, 10 lr, 20 lr; weight decay on groups 0 and 2."""
+    param_groups = model.get_parameter_groups()
+    return PolyOptimizer([
+        {'params': param_groups[0], 'lr': lr, 'weight_decay': wt_dec},
+        {'params': param_groups[1], 'lr': 2 * lr, 'weight_decay': 0},
+        {'params': param_groups[2], 'lr': 10 * lr, 'weight_decay': wt_dec},
+        {'params': param_groups[3], 'lr': 20 * lr, 'weight_decay': 0}
+    ], lr=lr, weight_decay=wt_dec, max_step=max_step)
