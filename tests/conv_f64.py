@@ -5,9 +5,10 @@ tests/test_gpu_conv_f64.py judges the kernels with them.
 References.  Everything is computed by torch on the CPU in float64 from operands ALREADY ROUNDED to the storage dtype (bf16 operands are bf16
 values, f32 and split-bf16 operands are f32 values), in the kernels' row layout: an activation is [rows = pixels of segment 1 then segment 2]
 [channels].  conv_problem() covers forward and data gradient (stride, dilation, padding, two row segments, a second 1x1 source) with every
-fused epilogue the network launches, and the stem; wgrad_problem() the weight gradient with IC_dw / OC_dw extents and accumulation onto
-existing content.  Next to each reference stands its ABSOLUTE-VALUE COMPANION S = conv(|x|, |w|) (weight gradient: A = sum |x| |dy|): the
-sum of the magnitudes of the products of one output, which is what accumulation error scales with.
+fused epilogue the network launches, and the stem; wgrad_problem() the weight gradient with IC_dw / OC_dw extents, two row segments, row
+strides and column offsets of the operands, the column rotation dw_rot, a forced split and accumulation onto existing content.  Next to
+each reference stands its ABSOLUTE-VALUE COMPANION S = conv(|x|, |w|) (weight gradient: A = sum |x| |dy|): the sum of the magnitudes of the
+products of one output, which is what accumulation error scales with.
 
 How the bars are set (the convention of tests/f64_bars.py: from the kernel's arithmetic, SAFETY = 2 on the error terms, never fitted to a
 run).  U32 = 2^-24.  A bar is  bar = ROUND(|ref| + e) + e,  e = the error of the f32 value the kernel holds before it stores.
@@ -49,7 +50,13 @@ CPU emulations (emulate_conv / emulate_wgrad): the honest kernel is torch's floa
 float32 convolutions of the split parts), the epilogue in float32, and the kernel's store (RNE to bf16).  The planted defects are the ones
 tests/test_gpu_conv.py's fitted bars let through: `trunc` a truncating bf16 store, `scale` every result times 1 + 2^-8, `drop_product` one
 (tap, channel) product missing from every output, `drop_lohi` the lo.hi term of split-bf16 missing, `drop_pixel` one output pixel's
-contribution missing from the weight gradient.  What a case can see is its `judges`: trunc needs a bf16 store and n <= N_CHAIN (beside
+contribution missing from the weight gradient.  The weight gradient's address paths (conv_wgrad_kernels.h stages its operands in three ways,
+chosen by geometry) have defects of their own: `seam_pixel` the first output pixel of the second row segment takes its x window with the
+first segment's width (a missed re-decode, a wrong pointer correction at the seam), `wrap_pixel` the first output pixel of image 1 takes the
+window of the pixel before it (a wrong image wrap of the incremental advance), `pad_wrap` a tap past the right border reads the next row's
+first pixels instead of zero (a validity test gone wrong), `drop_tail` the partial last K-tile adds nothing, `rot_off` dw's columns rotated
+by dw_rot - 1.
+What a case can see is its `judges`: trunc needs a bf16 store and n <= N_CHAIN (beside
 e_acc = 2 n U32 S of a long chain a missing half ulp is no longer visible; f32 storage has no storage rounding to get wrong); scale and
 drop_product are seen by every case, drop_lohi by every split-bf16 forward / data-gradient case; what a weight-gradient case sees follows
 from its pixel count (_wcase).
@@ -136,6 +143,7 @@ CONV_CASES = [
     _case("two_src_3x3_dgrad", "dgrad", "bf16", 2, 19, 16, 256, 128, 3, 1, 1, (0,), seg2=(7, 10), IC2=128),
     # the joint grid's data gradient (with WGRAD_CASES["pair"])
     _case("pair_dgrad", "dgrad", "bf16", 2, 132, 128, 256, 256, 3, 1, 1, (0,)),
+    _case("pair_seg2_dgrad", "dgrad", "bf16", 2, 119, 125, 256, 256, 1, 1, 1, (0,), seg2=(36, 44)),   # (with WGRAD_CASES["pair_seg2"])
 ]
 
 
@@ -158,33 +166,111 @@ def epi_cases():
 STEM_CASES = [_case(f"stem_{st}", "fwd", "f32", 2, 37, 70, 3, 64, 3, 1, 1, (0,), opset="stem", store=st) for st in ("f32", "bf16")]
 
 
-def _wcase(name, dt, N, H, W, IC, OC, k, s, d, hints, IC_dw=0, OC_dw=0):
-    c = SimpleNamespace(name=name, dt=dt, N=N, H=H, W=W, IC=IC, OC=OC, k=k, s=s, d=d, hints=hints, IC_dw=IC_dw or IC, OC_dw=OC_dw or OC)
+WGRAD_PK = {"bf16": 64, "f32": 32, "x3": 32}      # pixels per K-step of the weight-gradient kernels (conv_wgrad_kernels.h)
+WGRAD_FEATURES = ("1x1", "stride2", "dilated", "tiny", "seam", "split8", "ctail", "extents", "rot", "views")
+
+
+def _wcase(name, dt, N, H, W, IC, OC, k, s, d, hints, IC_dw=0, OC_dw=0, seg2=None, ld_x=0, ld_dy=0, x_off=0, dy_off=0, dw_rot=0, split_k=0,
+           unit=None, nsplit=None, nwg=None, tiny_seg=None):
+    """A weight-gradient case.  seg2 = (H2, W2): a second row segment (same N); ld_x / ld_dy / x_off / dy_off: the operand is the column
+    block [off, off + channels) of rows ld wide; dw_rot: column rotation of dw; split_k: the first launch's split (0 = the planner's).
+    unit / nsplit / nwg: what the plan of the first launch must report (None: not stated); tiny_seg: the segment (0 / 1) whose map is so
+    small that one K-step of 64 pixels wraps more than one image (the header's rule, 64 // OW + 1 > OH)."""
+    c = SimpleNamespace(name=name, dt=dt, N=N, H=H, W=W, IC=IC, OC=OC, k=k, s=s, d=d, hints=hints, IC_dw=IC_dw or IC, OC_dw=OC_dw or OC,
+                        seg2=seg2, ld_x=ld_x or IC, ld_dy=ld_dy or OC, x_off=x_off, dy_off=dy_off, dw_rot=dw_rot, split_k=split_k,
+                        unit=unit, nsplit=nsplit, nwg=nwg, tiny_seg=tiny_seg)
     # what the case can see, with n = the roundings of wgrad_bar and r = SAFETY acc_rel(n), the bar relative to A.  An element three sigma
     # out has |ref| = sqrt(n_pix) sigma_x sigma_dy 3 = sqrt(n_pix) and A = n_pix / 4 (uniform operands): |ref| / A = 4 / sqrt(n_pix), so a
     # scale defect shows where 2^-8 4 / sqrt(n_pix) > r.  A dropped pixel removes up to |x dy| = 1 = 4 A / n_pix: it shows where
     # 4 / n_pix > r.  A dropped lo.hi term is a random sum of n_pix terms of about 2^-10 |x dy|, some 2^-10 A / sqrt(n_pix) relative.
+    # The address defects (seam_pixel, wrap_pixel, pad_wrap, drop_tail) each replace or remove the x window of at least one output pixel, and
+    # rot_off moves every column: whoever sees a dropped pixel sees them, where the geometry has the feature at all.
     pad = d * (k // 2)
-    c.n_pix = N * _osz(H, k, s, d, pad) * _osz(W, k, s, d, pad)
+    c.sizes = [(H, W)] + ([seg2] if seg2 else [])
+    c.osizes = [(_osz(h, k, s, d, pad), _osz(w_, k, s, d, pad)) for h, w_ in c.sizes]
+    c.n_pix = sum(N * oh * ow for oh, ow in c.osizes)
     r = SAFETY * (acc_rel((3 if dt == "x3" else 1) * c.n_pix + 1) + (X3_MISSING if dt == "x3" else 0.0))
     c.judges = set()
     if 2.0 ** -8 * 4 / math.sqrt(c.n_pix) > r:
         c.judges.add("scale")
     if 4.0 / c.n_pix > r:
         c.judges.add("drop_pixel")
+        if seg2 and k > 1 and seg2[1] != W:                         # (the top row of a 1x1 window is the same at any width)
+            c.judges.add("seam_pixel")
+        if N > 1:
+            c.judges.add("wrap_pixel")
+        if any((ow - 1) * s + (k - 1) * d - pad >= w_ for (_h, w_), (_oh, ow) in zip(c.sizes, c.osizes)):
+            c.judges.add("pad_wrap")
+        if c.n_pix % WGRAD_PK[dt]:
+            c.judges.add("drop_tail")
+        if dw_rot:
+            c.judges.add("rot_off")
     if dt == "x3" and 2.0 ** -10 * 4 / math.sqrt(c.n_pix) > r:
         c.judges.add("drop_lohi")
     return c
 
 
-WGRAD_CASES = {c.name: c for c in [
+def wgrad_pipe(c, hint):
+    """does the run (case, tile_hint) name the 256x256 kernel"""
+    return hint == 256 and c.dt == "bf16" and c.IC >= 256 and c.OC >= 256
+
+
+def wgrad_features(c, hint):
+    """the features of WGRAD_FEATURES a run has, from the case's attributes"""
+    tile = 256 if wgrad_pipe(c, hint) else 128
+    has = {"1x1": c.k == 1, "stride2": c.s == 2, "dilated": c.d > 1 and c.k > 1, "tiny": c.tiny_seg is not None, "seam": c.seg2 is not None,
+           "split8": c.split_k == 8, "ctail": c.IC % tile != 0 or c.OC % tile != 0, "extents": c.IC_dw < c.IC or c.OC_dw < c.OC,
+           "rot": c.dw_rot != 0, "views": c.ld_x > c.IC or c.ld_dy > c.OC}
+    return {f for f, on in has.items() if on}
+
+
+def _wcases(name, dts, *args, **kw):
+    """one case per dtype, named name_<dtype> where there are several"""
+    return [_wcase(name if len(dts) == 1 else f"{name}_{dt}", dt, *args, **kw) for dt in dts]
+
+
+_OLD_WGRAD = [
     _wcase("wg_tail320", "bf16", 2, 10, 10, 320, 320, 3, 1, 1, (128, 256)),        # 64-wide tail in both tile dimensions, partial K-tile
     _wcase("wg_dil2", "bf16", 1, 13, 11, 256, 512, 3, 1, 2, (128, 256)),
     _wcase("wg_extents", "bf16", 2, 12, 10, 256, 256, 3, 1, 1, (128, 256), IC_dw=248, OC_dw=200),
     _wcase("wg_f32", "f32", 2, 20, 20, 64, 128, 3, 1, 1, (128,)),
     _wcase("wg_x3", "x3", 2, 20, 20, 64, 128, 3, 1, 1, (128,)),
     _wcase("pair", "bf16", 2, 132, 128, 256, 256, 3, 1, 1, (0,)),
-]}
+]
+for _c in _OLD_WGRAD:                 # (every one of them that reaches the 256x256 kernel stages with StageUnit)
+    _c.unit = 1
+B, BF, BFX = ("bf16",), ("bf16", "f32"), ("bf16", "f32", "x3")
+# The smallest shapes at which each address path of conv_wgrad_kernels.h is still taken.  128x128 kernel (conv_wgrad_kernel, any dtype):
+_NEW_128 = (
+    _wcases("wg_1x1_head", B, 2, 9, 9, 256, 152, 1, 1, 1, (128,), OC_dw=149, nsplit=1)      # taps = 1, 24-wide OC tail tile with the extent inside it, 162 px = 2 K-tiles + 34
+    + _wcases("wg_s2", BFX, 2, 21, 19, 64, 128, 3, 2, 1, (128,), nsplit=1)                  # 11x10 out: strided taps on odd sizes, both K-step widths
+    + _wcases("wg_1x1_s2", BF, 1, 21, 19, 64, 192, 1, 2, 1, (128,), nsplit=1)
+    + _wcases("wg_dil4", B, 2, 14, 14, 64, 128, 3, 1, 4, (128,), nsplit=1)                  # most taps are padding
+    + _wcases("wg_tiny", BF, 6, 5, 5, 64, 128, 3, 1, 1, (128,), nsplit=1, tiny_seg=0)       # one K-step spans 2.56 / 1.28 images: both `while` loops iterate
+    + _wcases("wg_seg2", BFX, 2, 12, 10, 64, 128, 3, 1, 1, (128,), seg2=(5, 4), nsplit=1, tiny_seg=1)   # seam at row 240 = 3 64 + 48 = 7 32 + 16: mid-tile
+    + _wcases("wg_seg2_s2", B, 2, 21, 19, 64, 128, 3, 2, 1, (128,), seg2=(9, 9), nsplit=1, tiny_seg=1)  # seam at 220, strided, second map 5x5
+    + _wcases("wg_rot", BF, 2, 9, 9, 256, 192, 1, 1, 1, (128,), IC_dw=195, dw_rot=3, nsplit=1)          # the f9 form: x columns 195..255 must not reach dw
+    + _wcases("wg_views", BF, 2, 9, 9, 72, 128, 1, 1, 1, (128,), ld_x=80, ld_dy=256, dy_off=64, nsplit=1)  # the f8_4 form, NaN outside the blocks
+    + _wcases("wg_split8", B, 2, 16, 15, 64, 128, 3, 1, 1, (128,), split_k=8, nsplit=8, nwg=72)         # nsplit % 8 == 0 block map, last split 32 rows
+)
+# 256x256 kernel (conv_wgrad_pipe_kernel, bf16, tile_hint 256): unit 1 = StageUnit, 0 = StageGeneral
+_NEW_256 = (
+    _wcases("wgp_s2", B, 2, 21, 19, 320, 256, 3, 2, 1, (256,), unit=0, nsplit=1)            # branch-free advance; IC tail with an absent channel half
+    + _wcases("wgp_1x1_s2", B, 2, 21, 19, 256, 320, 1, 2, 1, (256,), IC_dw=250, OC_dw=300, unit=0, nsplit=1)    # OC tail, extents in the general epilogue
+    + _wcases("wgp_dil2_s2", B, 2, 21, 19, 256, 256, 3, 2, 2, (256,), unit=0, nsplit=1)     # dilated strided taps (no dilated StageGeneral layer otherwise)
+    + _wcases("wgp_tiny", B, 6, 5, 5, 256, 256, 3, 1, 1, (256,), unit=0, nsplit=1, tiny_seg=0)          # simple_adv off: unit 0 although same-size stride 1
+    + _wcases("wgp_seg2_unit", B, 2, 12, 10, 256, 256, 3, 1, 2, (256,), seg2=(9, 8), ld_x=320, ld_dy=264, unit=1, nsplit=1)   # nA = 4 then nB = 3; xcross != 0
+    + _wcases("wgp_seg2_s2", B, 2, 21, 19, 256, 256, 3, 2, 1, (256,), seg2=(17, 15), unit=0, nsplit=1)  # simple_adv on, seam re-decode at 220
+    + _wcases("wgp_seg2_tiny", B, 2, 12, 10, 256, 256, 3, 1, 1, (256,), seg2=(5, 4), unit=0, nsplit=1, tiny_seg=1)    # simple_adv off, seam
+    + _wcases("wgp_split8", B, 2, 16, 15, 256, 256, 3, 1, 1, (256,), split_k=8, unit=1, nsplit=8, nwg=72)             # the other block map on the pipe kernel
+    + _wcases("wgp_split8_s2", B, 2, 31, 29, 256, 256, 3, 2, 1, (256,), split_k=8, unit=0, nsplit=8, nwg=72)          # the same on StageGeneral (16x15 out)
+)
+# the joint grid on two row segments: 1x1 (its float64 reference costs a ninth of a 3x3 one), M1 = 29750 = 464 64 + 54 is no multiple of 64.
+# (The pair plan fuses only where the data gradient plans onto 256-row tiles, at 256 -> 256 above 32768 pixels: 95x100 + 36x44 = 22168 pixels
+# is not fused, 119x125 + 36x44 = 32918 is the nearest geometry of that shape that is.)
+_PAIR_SEG2 = _wcases("pair_seg2", B, 2, 119, 125, 256, 256, 1, 1, 1, (0,), seg2=(36, 44), unit=1)
+WGRAD_CASES = {c.name: c for c in _OLD_WGRAD + _NEW_128 + _NEW_256 + _PAIR_SEG2}
+PAIR_CASES = ("pair", "pair_seg2")                 # run through wseg_conv_bwd_pair, not stand-alone
 
 
 # ------------------------------------------------------------------------------------------------------------------ forward / data gradient
@@ -352,22 +438,66 @@ def emulate_conv(p, defect=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------ weight gradient
+GATHER_DEFECTS = ("seam_pixel", "wrap_pixel", "pad_wrap")
+
+
 def wgrad_problem(c):
-    """x, dy (storage dtype, NCHW), the float64 weight gradient [OC][taps][IC] and its companion A = sum |x| |dy|"""
+    """xs, dys (storage dtype, NCHW, one per row segment; x, dy = the first segment's), the float64 weight gradient [OC_dw][taps][IC_dw]
+    (summed over the segments, columns rotated by dw_rot) and its companion A = sum |x| |dy|"""
     tdt = TORCH_DT[c.dt]
     pad = c.d * (c.k // 2)
-    p = SimpleNamespace(c=c, pad=pad, OH=_osz(c.H, c.k, c.s, c.d, pad), OW=_osz(c.W, c.k, c.s, c.d, pad))
-    p.x = rand((c.N, c.IC, c.H, c.W), 1).to(tdt)
-    p.dy = rand((c.N, c.OC, p.OH, p.OW), 3).to(tdt)
-    p.n_pix = c.N * p.OH * p.OW
-    p.ref = _wgrad(c, p.x, p.dy, torch.float64)
-    p.A = _wgrad(c, p.x.abs(), p.dy.abs(), torch.float64)
+    p = SimpleNamespace(c=c, pad=pad, OH=c.osizes[0][0], OW=c.osizes[0][1])
+    p.xs = [rand((c.N, c.IC, h, w_), 1 + i).to(tdt) for i, (h, w_) in enumerate(c.sizes)]
+    p.dys = [rand((c.N, c.OC, oh, ow), 3 + i).to(tdt) for i, (oh, ow) in enumerate(c.osizes)]
+    p.x, p.dy = p.xs[0], p.dys[0]
+    p.n_pix = c.n_pix
+    p.ref = _wgrad(c, p.xs, p.dys, torch.float64)
+    p.A = _wgrad(c, [x.abs() for x in p.xs], [dy.abs() for dy in p.dys], torch.float64)
     return p
 
 
-def _wgrad(c, x, dy, dtype):
-    g = torch.nn.grad.conv2d_weight(x.to(dtype), (c.OC, c.IC, c.k, c.k), dy.to(dtype), c.s, c.d * (c.k // 2), c.d)
-    return g.permute(0, 2, 3, 1).reshape(c.OC, c.k * c.k, c.IC)[:c.OC_dw, :, :c.IC_dw]
+def wgrad_rows(p):
+    """the operands in the kernels' row layout: x [input pixels of segment 1 then 2][IC], dy [output pixels likewise][OC]"""
+    return torch.cat([rows(x) for x in p.xs]), torch.cat([rows(dy) for dy in p.dys])
+
+
+def _wgrad(c, xs, dys, dtype, defect=None):
+    """dw [OC_dw][taps][IC_dw] of the operand lists (one entry per row segment) in `dtype`: reference column (ic + dw_rot) % IC_dw holds
+    input channel ic.  The address defects go through the explicit gather (_wgrad_gather), everything else through conv2d_weight."""
+    if defect in GATHER_DEFECTS:
+        g = sum(_wgrad_gather(c, i, x.to(dtype), dy.to(dtype), defect) for i, (x, dy) in enumerate(zip(xs, dys)))
+    else:
+        g = sum(torch.nn.grad.conv2d_weight(x.to(dtype), (c.OC, c.IC, c.k, c.k), dy.to(dtype), c.s, c.d * (c.k // 2), c.d)
+                .permute(0, 2, 3, 1).reshape(c.OC, c.k * c.k, c.IC) for x, dy in zip(xs, dys))
+    rot = c.dw_rot - 1 if defect == "rot_off" else c.dw_rot
+    return torch.roll(g[:c.OC_dw, :, :c.IC_dw], rot, dims=2)
+
+
+def _wgrad_gather(c, seg, x, dy, defect=None):
+    """The weight gradient of row segment `seg` as the kernels compute it: per tap, dy^T times the x rows gathered at
+    base(n) + iy W + ix, zero where the tap falls outside the image.  defect None is conv2d_weight (asserted on the CPU);
+      seam_pixel  the first output pixel of segment 2 takes its window with segment 1's width (row iy W1 + ix of its image);
+      wrap_pixel  the first output pixel of image 1 (segment 1) takes the window of the pixel before it, the last of image 0;
+      pad_wrap    a tap past the right border reads on in the row layout (the next row's first pixels), not zero."""
+    (H, W), (OH, OW), N, pad = c.sizes[seg], c.osizes[seg], c.N, c.d * (c.k // 2)
+    xr, dyr = rows(x), rows(dy)
+    n = torch.arange(N).repeat_interleave(OH * OW)
+    oy = torch.arange(OH).repeat_interleave(OW).repeat(N)
+    ox = torch.arange(OW).repeat(N * OH)
+    g = torch.zeros(c.OC, c.k * c.k, c.IC, dtype=x.dtype)
+    for tap in range(c.k * c.k):
+        iy, ix = oy * c.s + (tap // c.k) * c.d - pad, ox * c.s + (tap % c.k) * c.d - pad
+        ok = (iy >= 0) & (iy < H) & (ix >= 0) & (ix < W)
+        src = n * H * W + iy * W + ix
+        if defect == "pad_wrap":
+            ok = ok | ((iy >= 0) & (iy < H) & (ix >= W) & (src < N * H * W))
+        if defect == "seam_pixel" and seg == 1:
+            src[0] = iy[0] * c.W + ix[0]
+            ok[0] = ok[0] & (src[0] < N * H * W)
+        if defect == "wrap_pixel" and seg == 0 and N > 1:
+            src[OH * OW], ok[OH * OW] = src[OH * OW - 1], ok[OH * OW - 1]
+        g[:, tap, :] = dyr.t() @ (xr[src.clamp(0, N * H * W - 1)] * ok[:, None].to(x.dtype))
+    return g
 
 
 def wgrad_bar(p, splits, prior=None):
@@ -381,19 +511,37 @@ def wgrad_bar(p, splits, prior=None):
     return ref, stored_bar(ref, SAFETY * e, "f32")
 
 
+def _drop_rows(c, dys, first, count):
+    """dys with the output pixels [first, first + count) of the row layout set to zero"""
+    out, at = [], 0
+    for dy in dys:
+        r = rows(dy).clone()
+        lo, hi = max(first - at, 0), min(first + count - at, r.shape[0])
+        if lo < hi:
+            r[lo:hi] = 0
+        at += r.shape[0]
+        N, C, H, W = dy.shape
+        out.append(r.reshape(N, H, W, C).permute(0, 3, 1, 2))
+    return out
+
+
 def emulate_wgrad(p, defect=None, prior=None):
     c, f = p.c, torch.float32
-    dy = p.dy.float()
+    dys = [dy.float() for dy in p.dys]
     if defect == "drop_pixel":                      # one output pixel (image 0, centre) adds nothing
-        dy = dy.clone()
-        dy[0, :, p.OH // 2, p.OW // 2] = 0
+        dys[0] = dys[0].clone()
+        dys[0][0, :, p.OH // 2, p.OW // 2] = 0
+    if defect == "drop_tail":                       # the partial last K-tile adds nothing
+        tail = c.n_pix % WGRAD_PK[c.dt]
+        dys = _drop_rows(c, dys, c.n_pix - tail, tail)
     if c.dt == "x3":
-        (xh, xl), (dh, dl) = split_bf16(p.x), split_bf16(dy)
-        g = _wgrad(c, xh, dh, f) + _wgrad(c, xh, dl, f)
+        xh, xl = zip(*[split_bf16(x) for x in p.xs])
+        dh, dl = zip(*[split_bf16(dy) for dy in dys])
+        g = _wgrad(c, xh, dh, f, defect) + _wgrad(c, xh, dl, f, defect)
         if defect != "drop_lohi":
-            g = g + _wgrad(c, xl, dh, f)
+            g = g + _wgrad(c, xl, dh, f, defect)
     else:
-        g = _wgrad(c, p.x, dy, f)
+        g = _wgrad(c, p.xs, dys, f, defect)
     if defect == "scale":
         g = g * DEFECT_SCALE
     return (g if prior is None else g + prior.float()).double()

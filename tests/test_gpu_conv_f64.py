@@ -87,7 +87,7 @@ def _run_conv(p, bm):
             assert bool((bufs[name][:, :OFF] == GUARD).all()) and bool((bufs[name][:, OFF + c.out_ch:] == GUARD).all())
 
 
-CONV_RUNS = [(c, bm) for c in X.CONV_CASES + X.epi_cases() if c.name != "pair_dgrad" for bm in c.fams]
+CONV_RUNS = [(c, bm) for c in X.CONV_CASES + X.epi_cases() if not c.name.startswith("pair") for bm in c.fams]   # (pair*: _run_pair)
 
 
 @pytest.mark.parametrize("c,bm", CONV_RUNS, ids=[f"{c.name}-{bm}" for c, bm in CONV_RUNS])
@@ -111,53 +111,88 @@ def test_stem_f64(c):
         _check(f"{c.name} {fn.__name__} act", act, *p.refs["out2"])
 
 
-def _wgrad_kw(p):
-    c = p.c
-    return dict(N=c.N, IH=c.H, IW=c.W, IC=c.IC, OH=p.OH, OW=p.OW, OC=c.OC, KH=c.k, KW=c.k, stride=c.s, dil=c.d, pad=p.pad)
+def _wgrad_kw(c):
+    """the geometry keywords of a weight-gradient case (conv_wgrad, wgrad_plan, and the pair grid's weight-gradient half)"""
+    kw = dict(N=c.N, IH=c.H, IW=c.W, IC=c.IC, OH=c.osizes[0][0], OW=c.osizes[0][1], OC=c.OC, KH=c.k, KW=c.k, stride=c.s, dil=c.d,
+              pad=c.d * (c.k // 2), ld_x=c.ld_x, ld_dy=c.ld_dy, dw_rot=c.dw_rot)
+    if c.seg2:
+        kw["seg2"] = (*c.seg2, *c.osizes[1])
+    return kw
 
 
-WGRAD_RUNS = [(c, h) for c in X.WGRAD_CASES.values() if c.name != "pair" for h in c.hints]
+def _wgrad_launch_kw(c, hint):
+    from wseg_amd import _lib as L
+    return dict(IC_dw=c.IC_dw, OC_dw=c.OC_dw, tile_hint=hint, dtype={"f32": L.F32, "bf16": L.BF16, "x3": L.F32X3}[c.dt], **_wgrad_kw(c))
+
+
+def _view(block, ld, off, dev):
+    """`block` [rows][channels] as the column block [off, off + channels) of a matrix with rows `ld` wide whose every other element is NaN
+    (a correct kernel decides channel validity per 16-byte chunk against IC / OC and never loads them): (pointer view, the matrix)"""
+    if ld == block.shape[1] and off == 0:
+        t = block.contiguous().to(dev)
+        return t, t
+    wide = torch.full((block.shape[0], ld), float("nan"), dtype=block.dtype, device=dev)
+    wide[:, off:off + block.shape[1]] = block.to(dev)
+    return wide.view(-1)[off:], wide
+
+
+WGRAD_RUNS = [(c, h) for c in X.WGRAD_CASES.values() if c.name not in X.PAIR_CASES for h in c.hints]
 
 
 @pytest.mark.parametrize("c,hint", WGRAD_RUNS, ids=[f"{c.name}-{h}" for c, h in WGRAD_RUNS])
 def test_wgrad_f64(c, hint):
-    """the weight gradient on zeros with the planner's split, then once more with split_k = 3 on top of that content; dw narrower than the
-    operands where the case says so; a sentinel guard behind the buffer"""
+    """the weight gradient on zeros with the planner's split (or the one the case forces), then once more with split_k = 3 on top of that
+    content; dw narrower than the operands and rotated where the case says so; operands as column blocks of wider NaN-filled matrices where
+    it has row strides; a sentinel guard behind the buffer.  Kernel family and staging variant are asserted through the plan."""
     from wseg_amd import _lib as L
     p, dev = _problem(c), "cuda"
-    tdt = X.TORCH_DT[c.dt]
-    xg, dyg = X.rows(p.x).contiguous().to(dev), X.rows(p.dy).contiguous().to(dev)
+    xr, dyr = X.wgrad_rows(p)
+    (xg, _xkeep), (dyg, _dykeep) = _view(xr, c.ld_x, c.x_off, dev), _view(dyr, c.ld_dy, c.dy_off, dev)
     n, NG, SENTINEL = p.ref.numel(), 4096, -12345.0
     buf = torch.zeros(n + NG, device=dev, dtype=torch.float32)
     buf[n:] = SENTINEL
-    fam = WGRAD_PIPE if (hint == 256 and c.dt == "bf16" and c.IC >= 256 and c.OC >= 256) else WGRAD_128
-    kw = dict(IC_dw=c.IC_dw, OC_dw=c.OC_dw, tile_hint=hint, dtype=L.F32X3 if c.dt == "x3" else None, **_wgrad_kw(p))
+    pipe = X.wgrad_pipe(c, hint)
+    kw = _wgrad_launch_kw(c, hint)
     prior = None
-    for split_k in (0, 3):
-        splits = L.wgrad_plan(xg, dyg, buf, split_k=split_k, **kw).nsplit
-        _wgrad(fam, xg, dyg, buf, split_k=split_k, **kw)
+    for split_k in (c.split_k, 3):
+        plan = L.wgrad_plan(xg, dyg, buf, split_k=split_k, **kw)
+        assert plan.unit == (c.unit if pipe else 0), (c.name, hint, plan)
+        _wgrad(WGRAD_PIPE if pipe else WGRAD_128, xg, dyg, buf, split_k=split_k, **kw)
         got = buf[:n].reshape(p.ref.shape).double().cpu()
-        ref, bar = X.wgrad_bar(p, splits, prior)
-        _check(f"{c.name} hint={hint} split_k={split_k} ({splits} splits) dw", got, ref, bar)
+        ref, bar = X.wgrad_bar(p, plan.nsplit, prior)
+        _check(f"{c.name} hint={hint} split_k={split_k} ({plan.nsplit} splits) dw", got, ref, bar)
         prior = got
+    assert bool((buf[n:] == SENTINEL).all())
+
+
+def _run_pair(name):
+    from wseg_amd import _lib as L
+    pd, pw, dev = _problem(next(c for c in X.CONV_CASES if c.name == name + "_dgrad")), _problem(X.WGRAD_CASES[name]), "cuda"
+    c = pd.c
+    dy = torch.cat([X.rows(x) for x in pd.xs]).contiguous().to(dev)
+    xg, dyw = (t.contiguous().to(dev) for t in X.wgrad_rows(pw))
+    dkw, wkw = _launch_kw(pd, 0, dev), _wgrad_kw(pw.c)
+    wt = _weights(pd, dev)
+    dx = torch.full((pd.M, c.Cin), float("nan"), device=dev, dtype=torch.bfloat16)
+    n, NG, SENTINEL = pw.ref.numel(), 4096, -12345.0
+    buf = torch.zeros(n + NG, device=dev, dtype=torch.float32)
+    buf[n:] = SENTINEL
+    fused, dg_plan, wg_plan = L.conv_pair_plan(wkw, dy, wt, dx, **dkw)
+    assert fused == 1 and dg_plan.family in TILE_256 and wg_plan.family == WGRAD_PIPE and wg_plan.unit == pw.c.unit, (fused, dg_plan, wg_plan)
+    L.conv_igemm(dy, wt, dx, pair_wgrad=(xg, dyw, buf, wkw), **dkw)
+    _check(f"{name} dx", dx, *pd.refs["out"])
+    _check(f"{name} dw ({wg_plan.nsplit} splits)", buf[:n].reshape(pw.ref.shape), *X.wgrad_bar(pw, wg_plan.nsplit))
     assert bool((buf[n:] == SENTINEL).all())
 
 
 def test_conv_bwd_pair_f64():
     """wseg_conv_bwd_pair: data gradient and weight gradient of a layer in one grid (the smallest geometry the pair plan fuses)"""
-    from wseg_amd import _lib as L
-    pd, pw, dev = _problem(next(c for c in X.CONV_CASES if c.name == "pair_dgrad")), _problem(X.WGRAD_CASES["pair"]), "cuda"
-    c = pd.c
-    dy = X.rows(pd.xs[0]).contiguous().to(dev)
-    xg, dyw = X.rows(pw.x).contiguous().to(dev), X.rows(pw.dy).contiguous().to(dev)
-    geo = dict(N=c.N, KH=c.k, KW=c.k, stride=1, dil=c.d, pad=c.d * (c.k // 2))
-    dkw = dict(IH=c.H, IW=c.W, IC=c.Cout, OH=c.H, OW=c.W, OC=c.Cin, mode=1, **geo)
-    wkw = _wgrad_kw(pw)
-    wt = _weights(pd, dev)
-    dx = torch.full((pd.M, c.Cin), float("nan"), device=dev, dtype=torch.bfloat16)
-    dw = torch.zeros(pw.ref.shape, device=dev, dtype=torch.float32)
-    fused, dg_plan, wg_plan = L.conv_pair_plan(wkw, dy, wt, dx, **dkw)
-    assert fused == 1 and dg_plan.family in TILE_256 and wg_plan.family == WGRAD_PIPE, (fused, dg_plan, wg_plan)
-    L.conv_igemm(dy, wt, dx, pair_wgrad=(xg, dyw, dw, wkw), **dkw)
-    _check("pair dx", dx, *pd.refs["out"])
-    _check(f"pair dw ({wg_plan.nsplit} splits)", dw, *X.wgrad_bar(pw, wg_plan.nsplit))
+    _run_pair("pair")
+
+
+def test_conv_bwd_pair_seg2_f64():
+    """the joint grid on two row segments: 1x1, N = 2, 119x125 + 36x44, 256 -> 256.  M1 = 29750 is no multiple of 64, so the seam falls
+    inside a K-tile of a straight walk and the weight-gradient half has to split its range there.  (95x100 + 36x44 = 22168 pixels is not
+    fused: the data gradient of a 256 -> 256 layer plans onto 256-row tiles, which the joint grid needs, only above 32768 pixels; this is the
+    nearest two-segment geometry of the same shape that conv_pair_plan reports as fused.)"""
+    _run_pair("pair_seg2")
