@@ -208,7 +208,7 @@ int wseg_resize_planar_bwd(const float* d_out, float* d_in, const float* plane_m
  * stats = wseg_plane_stats(sum_cam, 20 planes). */
 int wseg_infer_finish(const float* sum_cam, const float* stats, float alpha, float* norm_cam, unsigned char* pred, int npix, void* stream);
 
-/* ---- PCM (network/resnet38_contrast.py:63-75), flash-style, exact-f32 MFMA ---------------------
+/* ---- PCM (network/resnet38_contrast.py:63-75), flash-style: exact-f32 MFMA here, bf16 MFMA in the *_bf16 variants below ----
  * l2norm  : Fh = F/(||F||_2 + 1e-5) over the 192 f9 channels of each pixel row (:70)
  * forward : cam_rv[n][c][j] = sum_i G[i][c] relu(Fh_i.Fh_j) / (sum_i relu(Fh_i.Fh_j) + 1e-5)  (:71-73)
  * backward: gradient w.r.t. Fh only (the CAM input is no_grad in the reference, :41-48). */

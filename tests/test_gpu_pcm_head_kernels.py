@@ -357,12 +357,15 @@ def test_to_bf16_and_split_bf16(total):
     assert bool((res.abs()[normal] <= 2.0 ** -17 * xs.abs()[normal]).all())
 
 
-@pytest.mark.parametrize("hw", [15, 65, 117])
+@pytest.mark.parametrize("hw", PCM_HW)
 def test_pcm_bf16_forward_and_backward(hw):
     """The bf16-MFMA PCM against float64 from the same rounded operands: Fb = bf16(Fh) everywhere, Gb in the forward, Gb + Gl in
-    the backward's gate product (DN is split by the kernel itself).  Products of bf16 values are exact in f32, so S keeps its
+    the backward's gate product (DN is split by the entry point itself).  Products of bf16 values are exact in f32, so S keeps its
     chain of 192; relu(S) and W are rounded to bf16; t = Pl.Qh + Ph.Ql + Ph.Qh is three MFMAs (a chain of 96) and drops Pl.Ql.
-    Pairs inside the gate band with these inputs, measured on the CPU: none at hw = 15 and 65, 0.007 % at hw = 117 (cap 0.1 %)."""
+    Image 1 of the N = 2 forward launch is bit-equal to a launch on that image alone.
+    Share of pairs inside the gate band with these inputs (Fb = bf16(Fh), seeds 300 + hw), measured on the CPU: none at hw = 1, 15,
+    33, 64 and 65; 0.0073 % at hw = 117 and 0.0168 % at hw = 256 (the cap is 0.1 %).  Open gates: all at hw = 1 (the diagonal),
+    0.47-0.51 of the pairs at every other size."""
     L = _L()
     N = 2
     Fh, G, d_rv = _pcm_inputs(N, hw, 300 + hw)
@@ -377,6 +380,8 @@ def test_pcm_bf16_forward_and_backward(hw):
     rv_k, den_k = _run_pcm_forward(L.pcm_forward_bf16, Fb, Gb, N, hw)
     S_all = _check_pcm_forward(rv_k, den_k, F64, Gb64, N, hw, relu_rel=BF16_RND)
     _assert_balanced(S_all, hw)
+    rv1, den1 = _run_pcm_forward(L.pcm_forward_bf16, Fb[hw:], Gb[hw:], 1, hw)
+    assert torch.equal(_i32(rv1[0]), _i32(rv_k[1])) and torch.equal(_i32(den1[0]), _i32(den_k[1]))
 
     fwd = [_pcm_fwd64(F64[n * hw:(n + 1) * hw], Gs64[n * hw:(n + 1) * hw]) for n in range(N)]
     rv_in = torch.stack([f[0] for f in fwd]).float()

@@ -302,10 +302,7 @@ static __global__ void pack_x3_kernel(const float* src, unsigned char* dst, long
   const float x[4] = {v.x, v.y, v.z, v.w};
   unsigned short hi[4], lo[4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    hi[e] = f32_to_bf16(x[e]);
-    lo[e] = f32_to_bf16(x[e] - bf16_to_f32(hi[e]));
-  }
+  for (int e = 0; e < 4; ++e) split_bf16(x[e], hi[e], lo[e]);
   *reinterpret_cast<uint2*>(dst + g * 128 + q * 8) = make_uint2((unsigned)hi[0] | ((unsigned)hi[1] << 16), (unsigned)hi[2] | ((unsigned)hi[3] << 16));
   *reinterpret_cast<uint2*>(dst + g * 128 + 64 + q * 8) = make_uint2((unsigned)lo[0] | ((unsigned)lo[1] << 16), (unsigned)lo[2] | ((unsigned)lo[3] << 16));
 }
@@ -329,23 +326,43 @@ static __global__ void split_bf16_kernel(const float* __restrict__ in, bf16_t* _
     unsigned h[4], l[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const bf16_t h0 = f32_to_bf16(v[2 * j]), h1 = f32_to_bf16(v[2 * j + 1]);
+      bf16_t h0, h1, l0, l1;
+      split_bf16(v[2 * j], h0, l0);
+      split_bf16(v[2 * j + 1], h1, l1);
       h[j] = (unsigned)h0 | ((unsigned)h1 << 16);
-      l[j] = (unsigned)f32_to_bf16(v[2 * j] - bf16_to_f32(h0)) | ((unsigned)f32_to_bf16(v[2 * j + 1] - bf16_to_f32(h1)) << 16);
+      l[j] = (unsigned)l0 | ((unsigned)l1 << 16);
     }
     *reinterpret_cast<uint4*>(hi + i) = make_uint4(h[0], h[1], h[2], h[3]);
     *reinterpret_cast<uint4*>(lo + i) = make_uint4(l[0], l[1], l[2], l[3]);
   } else {
-    for (long k = i; k < total; ++k) {
-      const bf16_t h0 = f32_to_bf16(in[k]);
-      hi[k] = h0; lo[k] = f32_to_bf16(in[k] - bf16_to_f32(h0));
-    }
+    for (long k = i; k < total; ++k) split_bf16(in[k], hi[k], lo[k]);
   }
 }
 
 extern "C" int wseg_split_bf16(const float* in, void* hi, void* lo, long total, void* stream) {
   WSEG_CHECK(in && hi && lo && total > 0, "split_bf16: bad arguments");
   hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)((total / 8 + 256) / 256)), dim3(256), 0, (hipStream_t)stream, in, (bf16_t*)hi, (bf16_t*)lo, total);
+  WSEG_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- f32 -> bf16 copy (the PCM operands of the bf16 mode, the engine's weight mirror)
+static __global__ void to_bf16_kernel(const float* __restrict__ in, bf16_t* __restrict__ out, long total) {
+  const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i + 3 < total) {
+    const float4 v = *reinterpret_cast<const float4*>(in + i);
+    uint2 o;
+    o.x = (unsigned)f32_to_bf16(v.x) | ((unsigned)f32_to_bf16(v.y) << 16);
+    o.y = (unsigned)f32_to_bf16(v.z) | ((unsigned)f32_to_bf16(v.w) << 16);
+    *reinterpret_cast<uint2*>(out + i) = o;
+  } else {
+    for (long k = i; k < total; ++k) out[k] = f32_to_bf16(in[k]);
+  }
+}
+
+extern "C" int wseg_to_bf16(const float* in, void* out, long total, void* stream) {
+  WSEG_CHECK(in && out && total > 0, "to_bf16: bad arguments");
+  hipLaunchKernelGGL(to_bf16_kernel, dim3((unsigned)((total / 4 + 256) / 256)), dim3(256), 0, (hipStream_t)stream, in, (bf16_t*)out, total);
   WSEG_LAUNCH_CHECK();
   return 0;
 }

@@ -40,24 +40,26 @@ template <> struct elem<WSEG_BF16> {
 
 template <> struct elem<WSEG_F32X3> : elem<WSEG_F32> {};   // f32 storage; only the conv / wgrad inner products differ
 
-// f32 x 8 -> (hi, lo) bf16 x 8 with x = hi + lo to 16-17 bits: hi = RNE bf16(x), lo = RNE bf16(x - hi)
-__device__ __forceinline__ void split_bf16x8(const f32x4& p0, const f32x4& p1, bf16x8& hi, bf16x8& lo) {
-  const float x[8] = {p0[0], p0[1], p0[2], p0[3], p1[0], p1[1], p1[2], p1[3]};
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const bf16_t h = f32_to_bf16(x[e]);
-    hi[e] = (short)h;
-    lo[e] = (short)f32_to_bf16(x[e] - bf16_to_f32(h));
-  }
+// f32 -> (hi, lo) bf16 with x = hi + lo to 16-17 bits: hi = RNE bf16(x), lo = RNE bf16(x - hi).  The one definition of the split:
+// every split-precision path (conv / wgrad operands, weight packs, the PCM gate product) rounds through it.
+__device__ __forceinline__ void split_bf16(float x, bf16_t& hi, bf16_t& lo) {
+  const bf16_t h = f32_to_bf16(x);
+  hi = h;
+  lo = f32_to_bf16(x - bf16_to_f32(h));
 }
 
 __device__ __forceinline__ void split_bf16x8(const float (&x)[8], bf16x8& hi, bf16x8& lo) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
-    const bf16_t h = f32_to_bf16(x[e]);
+    bf16_t h, l;
+    split_bf16(x[e], h, l);
     hi[e] = (short)h;
-    lo[e] = (short)f32_to_bf16(x[e] - bf16_to_f32(h));
+    lo[e] = (short)l;
   }
+}
+__device__ __forceinline__ void split_bf16x8(const f32x4& p0, const f32x4& p1, bf16x8& hi, bf16x8& lo) {
+  const float x[8] = {p0[0], p0[1], p0[2], p0[3], p1[0], p1[1], p1[2], p1[3]};
+  split_bf16x8(x, hi, lo);
 }
 
 // 8 consecutive elements <-> 8 floats (16 B for bf16, 32 B for f32); p must be 16-B aligned.

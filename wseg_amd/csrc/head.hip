@@ -10,8 +10,8 @@ namespace {
 // ---- head GEMM rows [pixels][ld] (cols 0..20 = fc8 logits) -> cam_low [N][21][hw] + per-(n,c) max of relu
 template <int DT>
 __global__ void head_split_kernel(const void* __restrict__ head, int ld, int c0, float* __restrict__ cam, float* __restrict__ cmax, int hw, long total) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;     // over N*hw; a block never straddles...
-  const long n = idx / hw;                                          // (it may: handled by per-thread atomics below)
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;     // over N*hw; a wave may straddle two images:
+  const long n = idx / hw;                                          // then every thread does its own atomic below
   const int p = (int)(idx - n * hw);
   const bool ok = idx < total;
   for (int c = 0; c < 21; ++c) {
@@ -68,7 +68,7 @@ __host__ __device__ inline float resize_scale(int in_size, int out_size, bool al
   return (float)in_size / out_size;
 }
 
-// ---- x_s = bilinear(x -> h x w, align_corners=True) into feature rows [N*hw][ld] cols 0..2; zero cols [c_zero0, ld)
+// ---- x_s = bilinear(x -> h x w, align_corners=True) into cols [c_xs, c_xs + 3) of the feature rows [N*hw][ld]; zero cols [c_xs + 3, c_end)
 template <int DT>
 __global__ void pcm_xs_kernel(const float* __restrict__ x, void* __restrict__ feat, int ld, int c_xs, int c_end,
                               int H, int W, int h, int w, long total) {
