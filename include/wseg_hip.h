@@ -480,6 +480,36 @@ int wseg_crf_gaussian(const float* in, float* tmp, float* out, int planes, int H
 int wseg_crf_update(const unsigned char* labels, const float* outb, const float* outg, const float* nb, const float* ng, float* Qn,
                     float* Qg, float* Qout, float* logits, unsigned char* amax, int S, int n_labels, int npix, float gt_prob,
                     float w_bilateral, float w_gaussian, void* stream);
+/* the same update for ONE label set whose unary comes from probabilities (pydensecrf's unary_from_softmax, segmentation/lib/utils/DenseCRF.py:17):
+ * U[c] = -ln(min(max(prob[c][i], 1e-5), 1)), prob f32 [n_labels][npix]; everything else as wseg_crf_update with S = 1 (one kernel body). */
+int wseg_crf_update_prob(const float* prob, const float* outb, const float* outg, const float* nb, const float* ng, float* Qn, float* Qg,
+                         float* Qout, float* logits, unsigned char* amax, int n_labels, int npix, float w_bilateral, float w_gaussian,
+                         void* stream);
+
+/* ---- DeepLab multi-scale test fusion (segmentation/experiment/SEAM_deeplabv1_resnet38/test.py:71-104) in ONE launch --------------------
+ * Per pass (one scale, plain or x-flipped) the reference resamples the net's stride-8 logits bilinearly (align_corners=True) to the scaled
+ * input size (ih, iw) (deeplabv1.py:50), resamples that again (align_corners=True) to the original (H, W), un-flips an odd entry with
+ * torch.flip, then takes the mean over the passes, the softmax over classes and the arg-max.  Here every output pixel composes the two
+ * resamples itself: its 2 x 2 stage-2 taps of the (ih, iw) grid are each evaluated from their own 2 x 2 stage-1 taps of the coarse
+ * (fh, fw) grid — ATen's align_corners coordinate rule (scale = (in - 1) / (out - 1), 0 when out == 1, in f32) at both stages, the
+ * intermediate value rounded to f32 as the materialised map would be.  A flipped pass is SAMPLED at the mirrored output column W - 1 - x
+ * (what the flip after the resize does; the weights are not mirrored).  The passes are summed in array order and the sum divided by n_pass.
+ * rows: cls_conv pixel rows [images * fh * fw][ld] (ld % 8 == 0, ld >= n_cls rounded up to 8, 16-byte aligned), dtype WSEG_F32 or WSEG_BF16;
+ * img: the image inside the batch the rows belong to.  One thread per output pixel, the class sums in registers; no LDS, no atomics.
+ * Outputs (NULL: not written, amax is required): mean_logits / prob (the softmax of the mean) f32 [n_cls][H * W], amax uint8 [H * W] (the
+ * first maximum of the mean wins, torch.argmax's rule), margin f32 [H * W] = top-1 minus top-2 of the mean. */
+#define WSEG_SEG_MAX_PASSES 16
+#define WSEG_SEG_MAX_CLASSES 32
+typedef struct wseg_seg_pass {
+  const void* rows;
+  int32_t ld, dtype, img;
+  int32_t fh, fw;      /* coarse (stride-8) dims */
+  int32_t ih, iw;      /* intermediate dims: the scaled input's size */
+  int32_t flip;
+} wseg_seg_pass;
+size_t wseg_sizeof_seg_pass(void);
+int wseg_seg_fuse(const wseg_seg_pass* passes, int n_pass, int H, int W, int n_cls, float* mean_logits, float* prob, unsigned char* amax,
+                  float* margin, void* stream);
 
 /* ---- evaluation counters (eval.py:22-52): integer pixel counts, ADDED into a caller-owned device buffer of unsigned 64-bit cells, so one
  * buffer collects a whole dataset and is read back once.  Both run on `stream` and synchronise nothing.  The ground-truth axis has

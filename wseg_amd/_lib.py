@@ -6,6 +6,7 @@ wrapper raises RuntimeError(wseg_last_error()) on a non-zero status.
 import contextlib
 import ctypes as C
 import os
+import typing
 
 import torch
 
@@ -546,3 +547,56 @@ def crf_gaussian(inp, tmp, out, planes, H, W, sxy): _call("wseg_crf_gaussian", _
 def crf_update(labels, outb, outg, nb, ng, Qn, Qg, Qout, logits, amax, S, n_labels, npix, gt_prob, w_bilateral, w_gaussian):
     _call("wseg_crf_update", _v(labels), _v(outb), _v(outg), _v(nb), _v(ng), _v(Qn), _v(Qg), _v(Qout), _v(logits), _v(amax), S, n_labels, npix,
           _f(gt_prob), _f(w_bilateral), _f(w_gaussian))
+def crf_update_prob(prob, outb, outg, nb, ng, Qn, Qg, Qout, logits, amax, n_labels, npix, w_bilateral, w_gaussian):
+    """wseg_crf_update for one label set whose unary is -ln(clip(prob, 1e-5, 1)), prob f32 [n_labels][npix]."""
+    if prob.dtype != torch.float32 or not prob.is_contiguous() or prob.numel() != n_labels * npix:      # (raw pointers beyond this line)
+        raise RuntimeError(f"crf_update_prob: prob must be a contiguous float32 tensor of {n_labels} x {npix}")
+    _call("wseg_crf_update_prob", _v(prob), _v(outb), _v(outg), _v(nb), _v(ng), _v(Qn), _v(Qg), _v(Qout), _v(logits), _v(amax), n_labels, npix,
+          _f(w_bilateral), _f(w_gaussian))
+
+
+# ---------------------------------------------------------------------------------------------- DeepLab multi-scale fusion (csrc/seg.hip)
+SEG_MAX_PASSES, SEG_MAX_CLASSES = 16, 32         # WSEG_SEG_*
+
+
+class SegPassDesc(C.Structure):                  # wseg_seg_pass
+    _fields_ = [("rows", C.c_void_p), ("ld", C.c_int32), ("dtype", C.c_int32), ("img", C.c_int32), ("fh", C.c_int32), ("fw", C.c_int32),
+                ("ih", C.c_int32), ("iw", C.c_int32), ("flip", C.c_int32)]
+
+
+lib.wseg_sizeof_seg_pass.restype = C.c_size_t
+if lib.wseg_sizeof_seg_pass() != C.sizeof(SegPassDesc):
+    raise ImportError(f"wseg_seg_pass: library {lib.wseg_sizeof_seg_pass()} bytes, binding {C.sizeof(SegPassDesc)}: rebuild libwseg_hip.so")
+
+
+class SegPass(typing.NamedTuple):
+    """One pass of seg_fuse: the cls_conv pixel rows [images * fh * fw, ld] (f32 or bf16), the image inside that batch, the coarse dims, the
+    intermediate dims (the scaled input's size) and whether the pass saw the x-flipped image."""
+    rows: torch.Tensor
+    ld: int
+    img: int
+    fh: int
+    fw: int
+    ih: int
+    iw: int
+    flip: bool
+
+
+def seg_fuse(passes, H, W, n_cls, amax, mean_logits=None, prob=None, margin=None):
+    """wseg_seg_fuse: the two-stage align_corners resample of every pass, un-flip, mean, softmax and arg-max in one launch; the
+    descriptors travel as launch arguments.  amax uint8 [H * W]; mean_logits / prob f32 [n_cls, H * W]; margin f32 [H * W]."""
+    if not 1 <= len(passes) <= SEG_MAX_PASSES:
+        raise RuntimeError(f"seg_fuse: {len(passes)} passes outside [1, {SEG_MAX_PASSES}]")
+    arr = (SegPassDesc * len(passes))()
+    nc8 = (n_cls + 7) // 8 * 8
+    for i, p in enumerate(passes):               # (raw pointers beyond this loop)
+        if p.rows.numel() < (p.img + 1) * p.fh * p.fw * p.ld or p.ld < nc8 or p.img < 0 or not p.rows.is_contiguous() or not p.rows.is_cuda:
+            raise RuntimeError(f"seg_fuse: pass {i}: rows of {p.rows.numel()} elements do not hold image {p.img} of {p.fh} x {p.fw} x ld {p.ld} (>= {nc8})")
+        arr[i] = SegPassDesc(p.rows.data_ptr(), p.ld, dtype_code(p.rows), p.img, p.fh, p.fw, p.ih, p.iw, int(p.flip))
+    for name, t_, n, dt in (("amax", amax, H * W, torch.uint8), ("mean_logits", mean_logits, n_cls * H * W, torch.float32),
+                            ("prob", prob, n_cls * H * W, torch.float32), ("margin", margin, H * W, torch.float32)):
+        if t_ is not None and (t_.dtype != dt or t_.numel() != n or not t_.is_contiguous() or not t_.is_cuda):
+            raise RuntimeError(f"seg_fuse: {name} must be a contiguous {dt} device tensor of {n} elements")
+    if amax is None:
+        raise RuntimeError("seg_fuse: the arg-max output is required")
+    _call("wseg_seg_fuse", arr, len(passes), H, W, n_cls, _v(mean_logits), _v(prob), _v(amax), _v(margin))

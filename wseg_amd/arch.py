@@ -45,6 +45,18 @@ AFF_HEAD_CONVS = OrderedDict([                   # resnet38_aff.py:13-17 (Affini
     ("f8_5", (256, 4096)),
     ("f9",   (448, 448)),
 ])
+# DeepLab-v1 head (segmentation/lib/net/deeplabv1.py:18-23) on t = relu(bn7(conv6)): (cout, cin, k) — conv_fov is 3x3 at dilation 12, each of
+# the first two convs is followed by a BatchNorm + ReLU, cls_conv alone has a bias
+SEG_HEAD_CONVS = OrderedDict([
+    ("conv_fov",  (512, 4096, 3)),
+    ("conv_fov2", (512, 512, 1)),
+    ("cls_conv",  (21,  512, 1)),
+])
+SEG_HEAD_BNS = {"conv_fov": ("bn_fov", 512), "conv_fov2": ("bn_fov2", 512)}      # the BatchNorm registered behind a head conv
+SEG_HEAD_BIAS = ("cls_conv",)
+SEG_HEAD_DILATION = 12
+SEG_BACKBONE_PREFIX = "backbone."
+SEG_CLS_ROWS = 24                                # cls_conv's pack and pixel rows, zero-padded: the conv launches need OC % 8 == 0
 NUM_CLASSES = 21
 PROJ_DIM = 128
 BN_EPS = 1e-5
@@ -81,9 +93,11 @@ def block_bns(b):
             (f"{name}.bn_branch2b2", cout // 2)]
 
 
-def state_dict_spec(head_convs=None):
+def state_dict_spec(head_convs=None, head_bns=None, head_bias=(), backbone_prefix=""):
     """OrderedDict key -> shape, in the reference's state_dict() order (233 keys with the contrast head).
-    head_convs: the net's head table (default HEAD_CONVS; AFF_HEAD_CONVS for the AffinityNet)."""
+    head_convs: the net's head table (default HEAD_CONVS; AFF_HEAD_CONVS for the AffinityNet): name -> (cout, cin) of a 1x1 conv or
+    (cout, cin, k).  head_bns {conv name: (bn name, channels)}: a BatchNorm registered behind that conv; head_bias: the head convs with
+    a bias; backbone_prefix: the backbone is a sub-module of that name (seg_state_dict_spec: the DeepLab head, 242 keys)."""
     spec = OrderedDict()
     spec["conv1a.weight"] = (64, 3, 3, 3)
 
@@ -111,9 +125,21 @@ def state_dict_spec(head_convs=None):
             elif p in convs:
                 spec[p + ".weight"] = convs[p]
     add_bn("bn7", 4096)
-    for hname, (co, ci) in (HEAD_CONVS if head_convs is None else head_convs).items():
-        spec[hname + ".weight"] = (co, ci, 1, 1)
+    if backbone_prefix:
+        spec = OrderedDict((backbone_prefix + k, v) for k, v in spec.items())
+    for hname, shape in (HEAD_CONVS if head_convs is None else head_convs).items():
+        co, ci, k = shape if len(shape) == 3 else (*shape, 1)
+        spec[hname + ".weight"] = (co, ci, k, k)
+        if hname in head_bias:
+            spec[hname + ".bias"] = (co,)
+        if head_bns and hname in head_bns:
+            add_bn(*head_bns[hname])
     return spec
+
+
+def seg_state_dict_spec():
+    """The 242 keys of the reference's deeplabv1 over resnet38d: `backbone.*`, then conv_fov, bn_fov, conv_fov2, bn_fov2, cls_conv (+ bias)."""
+    return state_dict_spec(SEG_HEAD_CONVS, SEG_HEAD_BNS, SEG_HEAD_BIAS, SEG_BACKBONE_PREFIX)
 
 
 def block_out_dims(b, dims):
@@ -139,7 +165,7 @@ def forward_macs(H, W, head_convs=None):
         h, w = oh, ow
     hw = h * w
     if head_convs is not None:
-        return macs + hw * sum(co * ci for (co, ci) in head_convs.values())
+        return macs + hw * sum(s[0] * s[1] * (s[2] ** 2 if len(s) == 3 else 1) for s in head_convs.values())
     macs += hw * sum(co * ci for (co, ci) in HEAD_CONVS.values())
     macs += hw * hw * (192 + 21)
     return macs

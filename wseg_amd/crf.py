@@ -69,26 +69,32 @@ class _Image:
         L.crf_rsqrt(sums, 16, self.nb, self.N)
 
 
-def _mean_field(im, labels, t, n_labels, gt_prob, wb, wg, want_logits):
-    S, N = labels.shape[0], im.N
+def _mean_field(im, labels, t, n_labels, gt_prob, wb, wg, want_logits, prob=None):
+    """t mean-field iterations of S label sets (labels [S, H, W]) or, with prob [n_labels, H, W], of the one set whose unary is
+    unary_from_softmax(prob) (labels, gt_prob unused) — the same filters and the same update kernel body either way."""
+    S, N = (1 if prob is not None else labels.shape[0]), im.N
     NC = L.crf_columns(S, n_labels)
-    f32 = dict(device=labels.device, dtype=torch.float32)
+    f32 = dict(device=im.img.device, dtype=torch.float32)
     Qn = torch.empty(im.npad // 4, NC, 4, **f32)
     Qg = torch.empty(S * n_labels, N, **f32)
     outb = torch.empty(im.npad, NC, **f32)
     outg, tmp = torch.empty_like(Qg), torch.empty_like(Qg)
     Q = torch.empty(S, n_labels, im.H, im.W, **f32)
     logits = torch.empty_like(Q) if want_logits else None
-    amax = torch.empty(S, im.H, im.W, device=labels.device, dtype=torch.uint8)
-    last = t == 0
-    L.crf_update(labels, None, None, im.nb, im.ng, Qn, Qg, Q if last else None, logits if last else None, amax if last else None,
-                 S, n_labels, N, gt_prob, wb, wg)
+    amax = torch.empty(S, im.H, im.W, device=im.img.device, dtype=torch.uint8)
+
+    def update(ob, og, last):
+        outs = (Q if last else None, logits if last else None, amax if last else None)
+        if prob is not None:
+            L.crf_update_prob(prob, ob, og, im.nb, im.ng, Qn, Qg, *outs, n_labels, N, wb, wg)
+        else:
+            L.crf_update(labels, ob, og, im.nb, im.ng, Qn, Qg, *outs, S, n_labels, N, gt_prob, wb, wg)
+
+    update(None, None, t == 0)
     for it in range(t):
-        last = it == t - 1
         L.crf_bilateral(im.feat, Qn, outb, N, NC, im.sxy, im.srgb)
         L.crf_gaussian(Qg, tmp, outg, S * n_labels, im.H, im.W, im.gauss_sxy)
-        L.crf_update(labels, outb, outg, im.nb, im.ng, Qn, Qg, Q if last else None, logits if last else None, amax if last else None,
-                     S, n_labels, N, gt_prob, wb, wg)
+        update(outb, outg, it == t - 1)
     return Q, logits, amax
 
 
@@ -119,6 +125,29 @@ def crf_inference(img_u8, labels, t=10, n_labels=21, gt_prob=0.7, bilateral=(80,
                  for s in range(0, labels.shape[0], per)]
     Q, logits, amax = parts[0] if len(parts) == 1 else tuple(torch.cat(x) if x[0] is not None else None for x in zip(*parts))
     out = (Q,) + ((logits,) if return_logits else ()) + ((amax,) if return_argmax else ())
+    return out[0] if len(out) == 1 else out
+
+
+@torch.no_grad()
+def crf_inference_from_probs(img_u8, prob, t=1, bilateral=(32, 13, 10), gaussian=(3, 3), return_logits=False, return_argmax=False):
+    """Mean-field inference of the DeepLab stage's dense_crf(probs, img, n_iters=1) (segmentation/lib/utils/DenseCRF.py:5-39) with exact
+    kernels: unary_from_softmax, U = -ln(clip(p, 1e-5, 1)), a Gaussian term (sxy 3, compat 3) and a bilateral term (sxy 32, srgb 13,
+    compat 10).  img_u8 [H, W, 3] uint8 and prob [M, H, W] float32 (2 <= M <= 32), both on the device.  Returns Q [M, H, W] float32 on
+    the device; with return_logits / return_argmax also the last iteration's logits and the uint8 [H, W] arg-max."""
+    if prob.dim() != 3 or prob.dtype != torch.float32 or prob.device != img_u8.device:
+        raise ValueError(f"prob must be float32 [M, H, W] on the image's device, got {prob.dtype} {tuple(prob.shape)}")
+    M = int(prob.shape[0])
+    if not 2 <= M <= L.CRF_MAX_LABELS:
+        raise ValueError(f"prob has {M} planes, outside [2, {L.CRF_MAX_LABELS}]")
+    if int(t) != t or t < 0:
+        raise ValueError(f"t={t} is not a non-negative integer")
+    if tuple(prob.shape[1:]) != tuple(img_u8.shape[:2]):
+        raise ValueError(f"prob {tuple(prob.shape[1:])} and image {tuple(img_u8.shape[:2])} differ in size")
+    (sxy, srgb, wb), (gsxy, wg) = bilateral, gaussian
+    with torch.cuda.device(img_u8.device):
+        im = _Image(img_u8, gsxy, sxy, srgb)
+        Q, logits, amax = _mean_field(im, None, int(t), M, None, float(wb), float(wg), return_logits, prob=prob.contiguous())
+    out = (Q[0],) + ((logits[0],) if return_logits else ()) + ((amax[0],) if return_argmax else ())
     return out[0] if len(out) == 1 else out
 
 

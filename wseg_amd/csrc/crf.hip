@@ -207,6 +207,7 @@ __global__ __launch_bounds__(256) void crf_labels_kernel(const float* __restrict
 
 struct CrfUpd {
   const unsigned char* labels;     // [S][N]
+  const float* prob;               // [M][N]: the unary's source in place of `labels` (crf_update_kernel<true>, S = 1)
   const float* outb;               // [npad][NC] unnormalised bilateral sums (null: the initial Q = softmax(-U))
   const float* outg;               // [S*M][N]   unnormalised Gaussian sums
   const float* nb; const float* ng;
@@ -217,6 +218,14 @@ struct CrfUpd {
   float pe, ne, wb, wg;
 };
 
+// -U[c] at pixel i: unary_from_labels (gt_prob at the pixel's label) or, PROB, unary_from_softmax: ln(clip(prob[c][i], 1e-5, 1))
+template <bool PROB>
+__device__ __forceinline__ float crf_neg_unary(const CrfUpd& a, int c, int lab, int i) {
+  if constexpr (PROB) return logf(fminf(fmaxf(a.prob[(size_t)c * a.N + i], 1e-5f), 1.f));
+  else return -(c == lab ? a.pe : a.ne);
+}
+
+template <bool PROB>
 __global__ __launch_bounds__(256) void crf_update_kernel(CrfUpd a) {
   const long t = (long)blockIdx.x * 256 + threadIdx.x;
   if (t >= (long)a.S * a.npad) return;
@@ -228,7 +237,7 @@ __global__ __launch_bounds__(256) void crf_update_kernel(CrfUpd a) {
     for (int c = 0; c < a.M; ++c) qn[(s * a.M + c) * 4] = 0.f;
     return;
   }
-  const int lab = a.labels[(size_t)s * a.N + i];
+  const int lab = PROB ? 0 : a.labels[(size_t)s * a.N + i];
   const float nbi = a.nb[i], ngi = a.ng[i];
   float lg[WSEG_CRF_MAX_LABELS];
   float mx = -INFINITY;
@@ -236,7 +245,7 @@ __global__ __launch_bounds__(256) void crf_update_kernel(CrfUpd a) {
 #pragma unroll
   for (int c = 0; c < WSEG_CRF_MAX_LABELS; ++c) {
     if (c < a.M) {
-      float v = -(c == lab ? a.pe : a.ne);
+      float v = crf_neg_unary<PROB>(a, c, lab, i);
       if (a.outb) {
         const float fg = ngi * a.outg[(size_t)(s * a.M + c) * a.N + i];
         const float fb = nbi * a.outb[(size_t)i * a.NC + s * a.M + c];
@@ -263,7 +272,7 @@ __global__ __launch_bounds__(256) void crf_update_kernel(CrfUpd a) {
   }
   if (a.logits) {                                            // recomputed: lg[] now holds the exponentials
     for (int c = 0; c < a.M; ++c) {
-      float v = -(c == lab ? a.pe : a.ne);
+      float v = crf_neg_unary<PROB>(a, c, lab, i);
       if (a.outb) {
         const float fg = ngi * a.outg[(size_t)(s * a.M + c) * a.N + i];
         const float fb = nbi * a.outb[(size_t)i * a.NC + s * a.M + c];
@@ -364,12 +373,30 @@ extern "C" int wseg_crf_update(const unsigned char* labels, const float* outb, c
              n_labels, WSEG_CRF_MAX_COLUMNS);
   WSEG_CHECK(gt_prob > 0.f && gt_prob < 1.f, "crf_update: gt_prob=%g outside (0, 1)", gt_prob);
   CrfUpd a;
+  a.prob = nullptr;
   a.labels = labels; a.outb = outb; a.outg = outg; a.nb = nb; a.ng = ng; a.Qn = Qn; a.Qg = Qg; a.Qout = Qout; a.logits = logits; a.amax = amax;
   a.S = S; a.M = n_labels; a.N = npix; a.npad = wseg_crf_padded_pixels(npix); a.NC = wseg_crf_columns(S, n_labels);
   a.pe = -logf(gt_prob); a.ne = -logf((1.f - gt_prob) / (float)(n_labels - 1));
   a.wb = w_bilateral; a.wg = w_gaussian;
   const long total = (long)S * a.npad;
-  hipLaunchKernelGGL(crf_update_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(crf_update_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  WSEG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int wseg_crf_update_prob(const float* prob, const float* outb, const float* outg, const float* nb, const float* ng, float* Qn,
+                                    float* Qg, float* Qout, float* logits, unsigned char* amax, int n_labels, int npix, float w_bilateral,
+                                    float w_gaussian, void* stream) {
+  WSEG_CHECK(prob && nb && ng && Qn && Qg && npix > 0, "crf_update_prob: null pointer / empty image");
+  WSEG_CHECK((outb == nullptr) == (outg == nullptr), "crf_update_prob: the two filter outputs come together (both null: initial Q)");
+  WSEG_CHECK(n_labels >= 2 && n_labels <= WSEG_CRF_MAX_LABELS, "crf_update_prob: n_labels=%d outside [2, %d]", n_labels, WSEG_CRF_MAX_LABELS);
+  CrfUpd a;
+  a.prob = prob;
+  a.labels = nullptr; a.outb = outb; a.outg = outg; a.nb = nb; a.ng = ng; a.Qn = Qn; a.Qg = Qg; a.Qout = Qout; a.logits = logits; a.amax = amax;
+  a.S = 1; a.M = n_labels; a.N = npix; a.npad = wseg_crf_padded_pixels(npix); a.NC = wseg_crf_columns(1, n_labels);
+  a.pe = a.ne = 0.f;
+  a.wb = w_bilateral; a.wg = w_gaussian;
+  hipLaunchKernelGGL(crf_update_kernel<true>, dim3((unsigned)((a.npad + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
   WSEG_LAUNCH_CHECK();
   return 0;
 }

@@ -68,8 +68,8 @@ def block_launch_convs(b, din, dout):
             for (name, cin, cout, k, stride, dil) in arch.block_convs(b)}
 
 
-def head_conv(name, cin, cout, dims):                        # a head layer: a 1x1 conv on the stride-8 maps
-    return Conv(name, cin, cout, 1, 1, 1, dims, dims)
+def head_conv(name, cin, cout, dims, k=1, dil=1):            # a head layer: a same-size conv on the stride-8 maps (1x1 but for DeepLab's conv_fov)
+    return Conv(name, cin, cout, k, 1, dil, dims, dims)
 
 
 class _Pass:
@@ -356,7 +356,7 @@ class Engine:
         net = self.net
         frozen_names = [c[0] for b in arch.BLOCKS if b[0] in arch.FROZEN_BLOCKS for c in arch.block_convs(b)]
         return (dt, str(device)) + tuple(b._version for b in net.buffers()) + \
-            tuple(p._version for n_, p in net.named_parameters() if ".bn" in n_ or n_.startswith("bn7")) + \
+            tuple(p._version for n_, p in net.named_parameters() if ".bn" in n_ or n_.startswith(("bn7", "bn_fov", "cls_conv.bias"))) + \
             tuple((self.conv_param(n_)._version, self.conv_param(n_).data_ptr()) for n_ in frozen_names) + \
             (net.conv1a.weight._version, net.conv1a.weight.data_ptr())
 
@@ -385,6 +385,14 @@ class Engine:
                         L.pack_weights(self.conv_param(cname).detach(), wf, None, co, k * k, ci, co, ci, L.F32 if dt == L.F32X3 else dt)
                         F_["w"][cname] = self._x3(wf) if dt == L.F32X3 else wf
             F_["bn"]["bn7"] = self._bn_fold("bn7", device)
+            if getattr(net, "HEAD_KIND", "contrast") == "seg":
+                # DeepLab head (deeplabv1.py:42-49): the two head BatchNorms folded like the backbone's; cls_conv's bias as the `shift` of its launch,
+                # zero-padded to the pack's rows
+                for bname, _c in arch.SEG_HEAD_BNS.values():
+                    F_["bn"][bname] = self._bn_fold(bname, device)
+                bias = torch.zeros(arch.SEG_CLS_ROWS, device=device, dtype=torch.float32)
+                bias[:arch.NUM_CLASSES] = net.cls_conv.bias.detach().float().to(device)
+                F_["bn"]["cls_conv"] = (None, bias)
             F_["w"]["conv1a_kc"] = net.conv1a.weight.detach().to(device).float().permute(2, 3, 1, 0).reshape(27, 64).contiguous()   # [k = (ky*3+kx)*3+ic][oc] for the packed-FMA stem
             self._frozen_packs, self._frozen_key = F_, fkey
             self.packs = None
@@ -461,6 +469,20 @@ class Engine:
                 for nm, (co, ci) in net.HEAD_CONVS.items():
                     off, n = self.offsets[nm]
                     P["w"][nm] = mirror[off:off + n].view(co, 1, ci)
+                return
+            if getattr(net, "HEAD_KIND", "contrast") == "seg":
+                # DeepLab head: conv_fov [512][9][4096] and conv_fov2 as views of the mirror; cls_conv's 21 rows copied into a pack zero-padded to
+                # 24 (every row is whole 32-element groups: the split-bf16 mirror's rows are copied as they are, and a zero row splits into zeros)
+                for nm, (co, ci, k) in net.HEAD_CONVS.items():
+                    off, n = self.offsets[nm]
+                    if co % 8 == 0:
+                        P["w"][nm] = mirror[off:off + n].view(co, k * k, ci)
+                        continue
+                    hb = self._head_bufs
+                    if hb is None or hb[0] != (dt, str(device)):
+                        hb = self._head_bufs = ((dt, str(device)), torch.zeros(arch.SEG_CLS_ROWS, k * k, ci, device=device, dtype=mirror.dtype))
+                    hb[1].view(-1)[:n].copy_(mirror[off:off + n])
+                    P["w"][nm] = hb[1]
                 return
             # fused head: rows [fc_proj | fc8 | 0]; its transposed pack is made from the two f32 masters directly
             hb = self._head_bufs                                 # persistent: the zero padding (rows / columns 149..191) is written once
@@ -810,6 +832,26 @@ class Engine:
         f9 = ps.E(M, C)
         conv(feat, "f9", f9, C, C)
         return feat, f9
+
+    def run_seg_head(self, t, dims, N, ps=None):
+        """The DeepLab-v1 head as a unit (segmentation/lib/net/deeplabv1.py:42-49, eval mode): conv_fov (3x3, dilation 12) + bn_fov + ReLU,
+        conv_fov2 (1x1) + bn_fov2 + ReLU, cls_conv (1x1 + bias) on t = relu(bn7(conv6)), pixel rows in the mode's dtype.  Each launch writes
+        only what the next one reads (`out2`, the affine form of the epilogue).  Returns the cls_conv pixel rows [M, 24] in the mode's dtype:
+        21 logits and three zero columns.  ps: the pass run_backbone returned; None: a pass on the current packs."""
+        if ps is None:
+            dev = t.device
+            P = self.ensure_packs(dev, DT_OF[self.net.precision])
+            self._join_late_packs(dev)
+            ps = _Pass(self, N, dev, DT_OF[self.net.precision], P)
+        M, bn = ps.rows_of(dims), ps.P["bn"]
+        (c1, ci1, k1), (c2, ci2, _k2), (_c3, ci3, _k3) = arch.SEG_HEAD_CONVS.values()
+        f1 = ps.E(M, c1)
+        ps.conv(head_conv("conv_fov", ci1, c1, dims, k=k1, dil=arch.SEG_HEAD_DILATION), t, None, f1, scale=bn["bn_fov"][0], shift=bn["bn_fov"][1])
+        f2 = ps.E(M, c2)
+        ps.conv(head_conv("conv_fov2", ci2, c2, dims), f1, None, f2, scale=bn["bn_fov2"][0], shift=bn["bn_fov2"][1])
+        rows = ps.E(M, arch.SEG_CLS_ROWS)
+        ps.conv(head_conv("cls_conv", ci3, arch.SEG_CLS_ROWS, dims), f2, None, rows, shift=bn["cls_conv"][1], relu_out2=0)
+        return rows
 
     def aff_head_wt(self, device):
         """P["wt"] of the four AffinityNet head convs, the data-gradient packs [IC][1][OC] in the mode's dtype (split-bf16: pre-split), made from the f32

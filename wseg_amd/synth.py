@@ -130,6 +130,41 @@ def procedural_aff_state_dict(seed=0, device="cpu"):
     return sd
 
 
+SEG_HEAD_GAIN = {"conv_fov": 1.0, "conv_fov2": 1.0, "cls_conv": 1.0}
+# Added to cls_conv's bias (seed 0's values; other seeds take them as they are).  With random weights the part of each logit that does not depend
+# on the pixel — a random projection of the features' channel MEANS — is about five times the spread over the pixels, so one class would win
+# every synthetic image and a label-map comparison would check nothing.  These constants are minus that part as the reference net computes it
+# (scripts/make_seg_goldens.py: the per-class spatial mean of the mean logits, averaged over its three cases, rounded to 0.5); what is left
+# of it on one image is as large as the spatial part, and several classes share the map.
+SEG_CLS_BIAS_CENTRE = (10.0, 7.0, 4.0, -8.5, 3.0, 0.5, -4.5, -7.0, 2.0, -0.5, 0.0, -8.0, 2.0, 3.0, -1.0, 3.0, 5.5, -6.5, -12.5, -0.5, 6.0)
+
+
+def procedural_seg_state_dict(seed=0, device="cpu"):
+    """State dict of the DeepLab-v1 net (segmentation/lib/net/deeplabv1.py over resnet38d): the backbone entries of procedural_state_dict(seed)
+    under `backbone.`, then the head under keys of its own ("seg." + name).  The head's two BatchNorms carry statistics as non-trivial as the
+    backbone's (weight, variance in [0.5, 1.5], bias, mean in [-0.2, 0.2]), cls_conv a bias in [-1, 1] plus SEG_CLS_BIAS_CENTRE, so that
+    the arg-max map of a synthetic image holds several classes."""
+    from .arch import SEG_BACKBONE_PREFIX, seg_state_dict_spec
+    sd = OrderedDict()
+    for k, shape in seg_state_dict_spec().items():
+        if k.startswith(SEG_BACKBONE_PREFIX):
+            sd[k] = procedural_tensor(k[len(SEG_BACKBONE_PREFIX):], shape, seed, device)
+            continue
+        head, leaf = k.split(".")
+        if leaf == "num_batches_tracked":
+            sd[k] = torch.zeros((), dtype=torch.int64, device=device)
+        elif head.startswith("bn_"):
+            lo, hi = (0.5, 1.5) if leaf in ("weight", "running_var") else (-0.2, 0.2)
+            sd[k] = _uniform("seg." + k, seed, shape, lo, hi, device)
+        elif leaf == "bias":
+            sd[k] = _uniform("seg." + k, seed, shape, -1.0, 1.0, device) + torch.tensor(SEG_CLS_BIAS_CENTRE, dtype=torch.float32, device=device)
+        else:
+            cout, cin, kh, kw = shape
+            a = SEG_HEAD_GAIN[head] * (6.0 / (cin * kh * kw)) ** 0.5
+            sd[k] = _uniform("seg." + k, seed, shape, -a, a, device)
+    return sd
+
+
 def synthetic_cam_dict(H, W, classes, seed=0, device="cpu"):
     """{class: float32 [H, W]} — what contrast_infer.py:82-90 writes per image (per-class normalised CAMs in [0, 1]), in closed form: per
     class one anisotropic Gaussian bump (centre / widths from the hash) plus a small hash texture, scaled to a maximum of 1."""
