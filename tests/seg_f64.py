@@ -5,7 +5,7 @@ over the passes, softmax over the classes, arg-max.  The yardstick of tests/test
 bar an f32 evaluation of the same math may differ by.  TEST INFRASTRUCTURE, no tests here."""
 import torch
 
-from tests.f64_bars import SAFETY, U32, _interp_bar
+from tests.f64_bars import SAFETY, U32, _coord_bar, _interp_bar
 
 
 def _axis(n_in, n_out):
@@ -44,3 +44,27 @@ def fuse_bar(passes, M):
     n = len(passes)
     per_pass = max(_interp_bar(c.shape[-2], c.shape[-1], M) + _interp_bar(ih, iw, M) for c, (ih, iw), _f in passes)
     return per_pass + SAFETY * n * U32 * M
+
+
+def _step(x):
+    """the largest |difference| of two neighbours of [..., h, w], along either axis"""
+    x = x.double()
+    dy = float((x[..., 1:, :] - x[..., :-1, :]).abs().max()) if x.shape[-2] > 1 else 0.0
+    dx = float((x[..., :, 1:] - x[..., :, :-1]).abs().max()) if x.shape[-1] > 1 else 0.0
+    return max(dy, dx)
+
+
+def fuse_bar_local(passes):
+    """`fuse_bar` for THESE logits instead of any logits bounded by M: the same terms, with what the worst case puts at 2M — |p1 - p0| of
+    the two samples an interpolation blends, which the source coordinate's rounding error multiplies — replaced by the largest neighbour
+    difference the pass's grid really has (stage 1: of the coarse logits; stage 2: of their float64 resample to the scaled input size),
+    and M by the pass's own max |logit|.  Never above fuse_bar(passes, max |logit|); on the fixtures of
+    tests/test_seg_host.py (a net's stride-8 logits resampled 8x) 6-12x below it."""
+    def sample(n_in, D, M):                  # f64_bars._interp_bar with D for 2M
+        return SAFETY * (2.0 * _coord_bar(n_in) * D + 6.0 * U32 * M)
+    per_pass, Mx = 0.0, 0.0
+    for c, (ih, iw), _f in passes:
+        M = float(c.abs().max())
+        Mx = max(Mx, M)
+        per_pass = max(per_pass, sample(max(c.shape[-2:]), _step(c), M) + sample(max(ih, iw), _step(resize(c, ih, iw)), M))
+    return per_pass + SAFETY * len(passes) * U32 * Mx

@@ -1,5 +1,6 @@
 """Host-side checks of the DeepLab-v1 inference stage (wseg_amd/deeplabv1_resnet38.py, wseg_amd/seg_infer.py) against the fixtures
-scripts/make_seg_goldens.py made by running the reference's deeplabv1 (tests/golden/seg_*.npz).  No GPU."""
+scripts/make_seg_goldens.py made by running the reference's deeplabv1 (tests/golden/seg_*.npz), and of the envelopes
+scripts/make_seg_envelopes.py made by running it in float64, float32, split-bf16 and bfloat16 (seg_*_env.npz, seg_*_tap64.npz).  No GPU."""
 import os
 
 import numpy as np
@@ -147,3 +148,93 @@ def test_conv_plan_accepts_the_head_launches():
                 plan = L.conv_plan(L._ANY, L._ANY, None, L._ANY, dtype=dt, shift=L._ANY, **kw, **extra)
                 assert plan.family in (L.CONV_64x128, L.CONV_128x128, L.CONV_224x256, L.CONV_256x256) and plan.nwg >= 1, (c.name, dt, plan)
     assert head_conv("conv_fov", 4096, 512, [(5, 7)], k=3, dil=12).fwd_kw(1)["pad"] == 12
+
+
+# ---- the reference's float64 / float32 / split-bf16 / bfloat16 runs: the envelopes the GPU bars are made of (tests/seg_env.py) ----
+
+def load_env(name):
+    """the reference's variants of a case with the envelopes computed from them (tests/seg_env.py:load_env)"""
+    from tests import seg_env
+    return seg_env.load_env(name)
+
+
+def test_envelope_table(capsys):
+    """prints what profiles/r20_seg_envelopes.txt records: per case the deviation of every variant from float64, coarse / mean / labels"""
+    from tests import seg_env
+    with capsys.disabled():
+        print()
+        for name in CASES:
+            e = load_env(name)
+            print(f"{name}: max |c64 logit| {e['M']:.2f}, max |mean64| {float(e['fused']['c64']['mean'].abs().max()):.2f}, fuse_bar {e['fuse_bar']:.3e} (for any logits that large {e['fuse_bar_worst']:.3e})")
+            for v in seg_env.VARIANTS[1:]:
+                print(f"  {v:9s} - c64: coarse {e['d_coarse'][v]:.3e}  mean {e['d_mean'][v]:.3e}  label disagreement "
+                      f"{seg_env.label_disagreement(e, e['fused'][v]['amax']):.2%}")
+            print(f"  ENV32 coarse {e['env32_coarse']:.3e} mean {e['env32_mean']:.3e};  bars fp32 {seg_env.bars(e, 'fp32')[0]:.3e} / {seg_env.bars(e, 'fp32')[1]:.3e}"
+                  f"  bf16x3 {seg_env.bars(e, 'bf16x3')[0]:.3e} / {seg_env.bars(e, 'bf16x3')[1]:.3e}")
+            t = e["tap"]
+            for i in t["tap_passes"]:
+                print(f"  tap pass {int(i)} {t[f'tap_{i}'].shape}: max |tap64| {float(t[f'tapmax_{i}']):.2f}  " +
+                      "  ".join(f"{v} {float(t[f'dev_{v}_{i}']):.3e}" for v in t["tap_variants"]))
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_envelopes_tie_to_the_fixture_and_the_chain_is_the_longest_order(name):
+    from tests import seg_env
+    from tests.f64_bars import SAFETY
+    e = load_env(name)
+    z = e["z"]
+    # the sequential K chain deviates at least as much as every vectorised order: otherwise the emulation is not doing what it says
+    for v in seg_env.F32_ORDERS:
+        assert e["d_coarse"]["f32_chain"] >= e["d_coarse"][v] > 0, v
+    assert e["env32_coarse"] == e["d_coarse"]["f32_chain"]
+    # the committed float32 fixture is one more float32 order of the same weights and inputs
+    d_fix = max(seg_env.coarse_dev(z["coarse"], e["coarse"]["c64"]))
+    print(f"{name}: max |fixture coarse - c64| {d_fix:.3e}, ENV32 {e['env32_coarse']:.3e}")
+    assert d_fix <= SAFETY * e["env32_coarse"]
+    # float64's label map is the fixture's outside the margins below twice the fp32 mean bar; those are at most 1 % of the pixels
+    ref = e["fused"]["c64"]
+    bar_mean = seg_env.bars(e, "fp32")[1]
+    unsure = ref["margin"] < 2 * bar_mean
+    print(f"{name}: fp32 mean bar {bar_mean:.3e}, {float(unsure.double().mean()):.3%} of the pixels below twice it")
+    assert float(unsure.double().mean()) <= 0.01
+    assert bool((ref["amax"] == torch.from_numpy(z["label"]).long())[~unsure].all())
+    assert 0 < e["fuse_bar"] <= e["fuse_bar_worst"]           # the collect's bar for these logits never exceeds the one for any logits that large
+    # the bars order as the arithmetic does, and stay far below the 1e-3 max |logit| line the fixtures' near-tie condition is stated at
+    assert e["d_coarse"]["f32_chain"] < e["d_coarse"]["x3"] < e["d_coarse"]["bf16"]
+    assert seg_env.bars(e, "bf16x3")[1] < 1e-3 * float(ref["mean"].abs().max())
+    # the tap: at least 256 channels of c64's conv_fov input, float64, the envelopes ordered the same way
+    t = e["tap"]
+    sizes = [tuple(-(-int(s) // 8) for s in z["sizes"][k]) for k in (0, len(z["sizes"]) - 1)]
+    assert [int(i) for i in t["tap_passes"]] == [0, 2 * (len(z["sizes"]) - 1)]
+    for i, (fh, fw) in zip(t["tap_passes"], sizes):
+        tap = t[f"tap_{i}"]
+        assert tap.dtype == np.float64 and tap.shape == (fh, fw, len(range(int(t["c0"]), 4096, int(t["stride"])))) and tap.shape[2] >= 256
+        assert set(range(int(t["c0"]), 4096, int(t["stride"]))[j] // 256 for j in range(tap.shape[2])) == set(range(16))
+        assert float(tap.min()) == 0.0 and float(tap.max()) <= float(t[f"tapmax_{i}"])          # a ReLU's output
+        assert 0 < float(t[f"dev_f32_chain_{i}"]) < float(t[f"dev_x3_{i}"]) < float(t[f"dev_bf16_{i}"])
+        for v in t["tap_variants"]:
+            assert float(t[f"devsub_{v}_{i}"]) <= float(t[f"dev_{v}_{i}"])
+    for f in os.listdir(GOLDEN):
+        if f.startswith(name):
+            assert os.path.getsize(os.path.join(GOLDEN, f)) < 1 << 20, f
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_the_bars_tell_a_wrong_mode_from_a_right_one(name):
+    """stored variants standing in for a GPU run (their collect in float64): the sequential float32 chain passes the fp32 rules and the
+    split-bf16 sum the bf16x3 rules; the reference's bfloat16 run fails both, and the split-bf16 sum fails fp32's"""
+    from tests import seg_env
+    e = load_env(name)
+
+    def run(mode, v):
+        f = e["fused"][v]
+        print(f"{name}: {v} judged as {mode}")
+        return seg_env.judge(e, mode, e["coarse"][v], f["mean"], f["amax"], f["margin"], f32_collect=False)
+    assert run("fp32", "f32_chain") == []
+    assert run("fp32", "c64") == []
+    assert run("bf16x3", "x3") == []
+    assert run("bf16x3", "f32_chain") == []
+    for mode in ("fp32", "bf16x3"):
+        failed = run(mode, "bf16")
+        assert "coarse" in failed and "mean" in failed, failed
+    assert "coarse" in run("fp32", "x3")
