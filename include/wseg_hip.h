@@ -511,6 +511,33 @@ size_t wseg_sizeof_seg_pass(void);
 int wseg_seg_fuse(const wseg_seg_pass* passes, int n_pass, int H, int W, int n_cls, float* mean_logits, float* prob, unsigned char* amax,
                   float* margin, void* stream);
 
+/* ---- DeepLab-v1 training loss (deeplabv1.py:50 + train.py:85,97): the cross-entropy (ignore_index 255, mean over the valid pixels of the
+ * BATCH) of the stride-8 logits resampled bilinearly (align_corners=True) to the label size, and its gradient on the coarse rows, without the
+ * full-size [N][n_cls][H][W] tensor: each label pixel samples its image's coarse rows itself (the source-index arithmetic of wseg_seg_fuse).
+ * rows:  cls_conv pixel rows [N*fh*fw][ld] in `dtype` (WSEG_F32 or WSEG_BF16), ld % 8 == 0, ld >= n_cls rounded up to 8, 16-byte aligned;
+ *        the classes are columns [0, n_cls), columns >= n_cls are never used.  2 <= n_cls <= WSEG_SEG_MAX_CLASSES.
+ * label: uint8 [N][H][W] device; 0 .. n_cls-1 a class, 255 ignore; a value in [n_cls, 255) is ignored as well and counted in out4[3].
+ * Any H, W >= 1 and fh, fw >= 1 (H < fh: a downsample); H, W, fh, fw < 2^24 and N*H*W < 2^31.
+ * lse:   f32 [N][H][W], the log-sum-exp over the classes of every pixel's sample (what the backward needs), or NULL for a loss-only call.
+ * out4 (f32 device): loss = sum / count, count of valid pixels, sum of nll = lse - z[label] over them, count of out-of-range labels.  The
+ *   counts are integer sums (out4 holds them converted to f32); the nll sum is reduced per workgroup in a fixed order into the workspace and
+ *   then by one workgroup in f64 in a fixed order: no atomics, bit-identical from run to run, nothing synchronises with the host.  A batch
+ *   without a valid pixel gives loss = 0 / 0 = NaN (torch's answer) and a zero gradient (torch's as well).
+ * Every argument check runs before the first device call. */
+long wseg_seg_ce_workspace_bytes(int N, int H, int W);                   /* -1 (and wseg_last_error) for a bad size */
+int wseg_seg_ce_forward(const void* rows, int ld, int dtype, const unsigned char* label, float* lse, void* workspace, float* out4, int N,
+                        int fh, int fw, int H, int W, int n_cls, void* stream);
+/* d_rows[N*fh*fw][ld_d] in d_dtype (WSEG_F32 or WSEG_BF16: the f32 sum rounded once) = gscale * d out4[0] / d rows (gscale: one f32 on the
+ * device, NULL = 1; count is read from out4 on the device).  GATHER form, one wave per coarse cell: the lanes walk the fine pixels whose taps
+ * include the cell — a conservative range, each pixel tested with the forward's own f32 source index, never an inverted scale — recompute
+ * the softmax from the four coarse rows and the saved lse, and add w_y * w_x * (softmax_c - [c == label]) in a fixed order; one fixed
+ * butterfly across the lanes, then one multiplication by gscale / count.  No atomics, bit-identical from run to run.  Columns
+ * [0, n_cls rounded up to 8) of EVERY row are written (zeros in the columns >= n_cls and in the rows of cells no valid pixel touches), the
+ * columns beyond are untouched.  ld_d % 8 == 0, ld_d >= n_cls rounded up to 8, d_rows 16-byte aligned. */
+int wseg_seg_ce_backward(const void* rows, int ld, int dtype, const unsigned char* label, const float* lse, const float* out4,
+                         const float* gscale, void* d_rows, int ld_d, int d_dtype, int N, int fh, int fw, int H, int W, int n_cls,
+                         void* stream);
+
 /* ---- evaluation counters (eval.py:22-52): integer pixel counts, ADDED into a caller-owned device buffer of unsigned 64-bit cells, so one
  * buffer collects a whole dataset and is read back once.  Both run on `stream` and synchronise nothing.  The ground-truth axis has
  * WSEG_EVAL_ROWS = 22 rows: 0..20 the classes, 21 = "a value in 21..254" (the evaluator counts such a pixel towards P of its predicted

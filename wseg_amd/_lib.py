@@ -600,3 +600,34 @@ def seg_fuse(passes, H, W, n_cls, amax, mean_logits=None, prob=None, margin=None
     if amax is None:
         raise RuntimeError("seg_fuse: the arg-max output is required")
     _call("wseg_seg_fuse", arr, len(passes), H, W, n_cls, _v(mean_logits), _v(prob), _v(amax), _v(margin))
+
+
+# ---------------------------------------------------------------------------------------------- DeepLab training loss (csrc/seg_loss.hip)
+lib.wseg_seg_ce_workspace_bytes.restype = C.c_long
+
+
+def seg_ce_workspace_bytes(N, H, W): return int(lib.wseg_seg_ce_workspace_bytes(N, H, W))
+def _seg_ce_extents(what, rows, ld, label, lse, N, fh, fw, H, W, n_cls):
+    """the extents the raw pointers of a seg_ce launch must cover (the library checks ld, alignment, n_cls and the sizes themselves)"""
+    nc8 = (n_cls + 7) // 8 * 8
+    if not rows.is_cuda or not rows.is_contiguous() or rows.numel() < (N * fh * fw - 1) * ld + nc8:
+        raise RuntimeError(f"{what}: rows of {rows.numel()} elements do not hold {N} x {fh} x {fw} contiguous device rows of ld {ld} (>= {nc8})")
+    if label.dtype != torch.uint8 or not label.is_cuda or not label.is_contiguous() or label.numel() != N * H * W:
+        raise RuntimeError(f"{what}: label must be a contiguous uint8 device tensor of {N} x {H} x {W}")
+    if lse is not None and (lse.dtype != torch.float32 or not lse.is_cuda or not lse.is_contiguous() or lse.numel() != N * H * W):
+        raise RuntimeError(f"{what}: lse must be a contiguous float32 device tensor of {N} x {H} x {W}")
+def seg_ce_forward(rows, ld, label, lse, ws, out4, N, fh, fw, H, W, n_cls):
+    """wseg_seg_ce_forward: out4 = loss, count, sum of nll, out-of-range labels; lse f32 [N, H, W] or None (a loss-only call)."""
+    _seg_ce_extents("seg_ce_forward", rows, ld, label, lse, N, fh, fw, H, W, n_cls)
+    need = seg_ce_workspace_bytes(N, H, W)
+    if need < 0 or ws.numel() * ws.element_size() < need or not ws.is_cuda or out4.dtype != torch.float32 or out4.numel() < 4 or not out4.is_cuda:
+        raise RuntimeError(f"seg_ce_forward: workspace of {need} bytes and a float32 out4 of 4 elements, both on the device ({lib.wseg_last_error().decode()})")
+    _call("wseg_seg_ce_forward", _v(rows), ld, dtype_code(rows), _v(label), _v(lse), _v(ws), _v(out4), N, fh, fw, H, W, n_cls)
+def seg_ce_backward(rows, ld, label, lse, out4, gscale, d_rows, ld_d, N, fh, fw, H, W, n_cls):
+    """wseg_seg_ce_backward: d_rows (f32 or bf16) [N*fh*fw][ld_d] = gscale * d loss / d rows, columns [0, n_cls rounded up to 8) of every row."""
+    _seg_ce_extents("seg_ce_backward", rows, ld, label, lse, N, fh, fw, H, W, n_cls)
+    nc8 = (n_cls + 7) // 8 * 8
+    if lse is None or not d_rows.is_cuda or not d_rows.is_contiguous() or d_rows.numel() < (N * fh * fw - 1) * ld_d + nc8:
+        raise RuntimeError(f"seg_ce_backward: lse, and contiguous device d_rows holding {N * fh * fw} rows of ld_d {ld_d} (>= {nc8})")
+    _call("wseg_seg_ce_backward", _v(rows), ld, dtype_code(rows), _v(label), _v(lse), _v(out4), _v(gscale), _v(d_rows), ld_d, dtype_code(d_rows),
+          N, fh, fw, H, W, n_cls)

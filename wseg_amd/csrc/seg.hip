@@ -1,8 +1,8 @@
 // seg.hip — DeepLab multi-scale test fusion (wseg_seg_fuse, include/wseg_hip.h): both bilinear resamples of every pass, the un-flip, the mean over the
 // passes, the softmax and the arg-max in one launch, from the stride-8 cls_conv pixel rows.  One thread per output pixel (x fastest: the planar
 // stores are full lines), the class sums in registers, the pass loop outermost; the coarse rows (24 contiguous elements) are read with 16-byte loads
-// and stay in L2 (at most 770 KB per pass).  No LDS, no atomics.
-#include "common.h"
+// and stay in L2 (at most 770 KB per pass).  No LDS, no atomics.  The source-index arithmetic (seg_src, seg_scale, seg_lerp2) is seg_geo.h's.
+#include "seg_geo.h"
 
 namespace {
 
@@ -11,22 +11,6 @@ struct SegArgs {
   int n_pass, H, W, n_cls;
   float* mean; float* prob; unsigned char* amax; float* margin;
 };
-
-// ATen's align_corners source index (area_pixel_compute_source_index + guard_index_and_lambda): s = scale * o in f32, i0 = min(floor(s), n - 1),
-// i1 = i0 + (i0 < n - 1), f = s - i0
-__device__ __forceinline__ void seg_src(int o, float scale, int n, int& i0, int& i1, float& f) {
-  const float s = scale * (float)o;
-  i0 = min((int)s, n - 1);
-  i1 = i0 + (i0 < n - 1 ? 1 : 0);
-  f = fminf(fmaxf(s - (float)i0, 0.f), 1.f);
-}
-__host__ __device__ inline float seg_scale(int n_in, int n_out) { return n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f; }
-
-// one bilinear sample, each product and sum rounded to f32 on its own (no contraction: the value does not depend on the compiler's fusing)
-__device__ __forceinline__ float seg_lerp2(float a, float b, float c, float d, float fy, float fx) {
-#pragma clang fp contract(off)
-  return (1.f - fy) * ((1.f - fx) * a + fx * b) + fy * ((1.f - fx) * c + fx * d);
-}
 
 struct SegTap { size_t r00, r01, r10, r11; float fy, fx; };   // element offsets of the four coarse rows of one intermediate pixel
 

@@ -6,7 +6,9 @@ segmentation/experiment/SEAM_deeplabv1_resnet38): `Net()`, `forward(x)` returnin
 bn_fov2, cls_conv with its bias), so a published checkpoint loads with strict=True.  The sub-modules are parameter containers: the
 backbone runs through wseg_amd.engine (the contrast net's kernels and packs), the head's three convs on the implicit-GEMM conv
 (Engine.run_seg_head: conv_fov is its 3x3 launch at dilation 12, both head BatchNorms folded into the epilogue, cls_conv's bias the
-epilogue's shift), the resample to the input size in csrc/seg.hip.  Inference only: in training mode `forward` raises.
+epilogue's shift), the resample to the input size in csrc/seg.hip.  Inference only: in training mode `forward` raises.  Of the training
+stage the loss layer exists — wseg_amd.seg_loss.seg_cross_entropy, the cross-entropy of the resampled coarse logits and its gradient on the
+cls_conv rows (csrc/seg_loss.hip) — the training forward (BatchNorm in batch mode, dropout) and the head's backward do not yet.
 """
 import os
 
@@ -16,6 +18,9 @@ import torch.nn as nn
 from . import arch
 from . import _lib as L
 from .resnet38_contrast import Net as _ContrastNet, Normalize, _Block
+
+_NO_TRAINING = ("wseg_amd.deeplabv1_resnet38.Net is inference-only: the training loss exists (wseg_amd.seg_loss.seg_cross_entropy on the coarse "
+                "logits), the training forward does not yet: call .eval() first")
 
 
 class _Backbone(nn.Module):
@@ -84,7 +89,7 @@ class Net(nn.Module):
     def forward(self, x):
         """deeplabv1.py:39-51 in eval mode: the logits resampled (bilinear, align_corners=True) to the input size, [N, 21, h, w] float32."""
         if self.training:
-            raise RuntimeError("wseg_amd.deeplabv1_resnet38.Net is inference-only (training the DeepLab stage is out of scope): call .eval() first")
+            raise RuntimeError(_NO_TRAINING)
         rows, (fh, fw) = self.coarse_logits(x)
         N, h, w = x.shape[0], x.shape[2], x.shape[3]
         out = torch.empty(N, arch.NUM_CLASSES, h, w, device=rows.device, dtype=torch.float32)
@@ -98,7 +103,7 @@ class Net(nn.Module):
         """(cls_conv pixel rows [N * fh * fw, 24] in the mode's dtype — 21 logits and three zero columns — and the stride-8 dims (fh, fw)); nothing
         synchronises.  seg_infer.fuse_image resamples and fuses them without the intermediate full-size maps."""
         if self.training:
-            raise RuntimeError("wseg_amd.deeplabv1_resnet38.Net is inference-only (training the DeepLab stage is out of scope): call .eval() first")
+            raise RuntimeError(_NO_TRAINING)
         if not x.is_cuda:
             raise RuntimeError("wseg_amd.deeplabv1_resnet38 runs only on an MI355X (HIP) device; there is no CPU fallback")
         x = x.contiguous().float()
