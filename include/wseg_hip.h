@@ -538,6 +538,42 @@ int wseg_seg_ce_backward(const void* rows, int ld, int dtype, const unsigned cha
                          const float* gscale, void* d_rows, int ld_d, int d_dtype, int N, int fh, int fw, int H, int W, int n_cls,
                          void* stream);
 
+/* ---- DeepLab-v1 head, training mode (deeplabv1.py:42-49 under train.py:52's plain nn.BatchNorm2d): what lies between the three convolutions,
+ * on pixel rows [M][ld] in WSEG_F32 or WSEG_BF16.  Rows are read and written in 8-column (16-byte) chunks: C % 8 == 0, every ld % 8 == 0 and
+ * >= C, every base 16-byte aligned (the per-column f32 vectors too, except the outputs of wseg_bn_stats and wseg_col_sums).  Every argument
+ * check runs before the first device call; nothing synchronises with the host; no kernel uses atomics and every reduction has a fixed order
+ * (per row chunk in f32 registers, the four waves of a workgroup in a fixed order, the chunks in f64, a column's by ONE workgroup), so every output is
+ * bit-identical from run to run.
+ * The workspace of wseg_bn_stats, wseg_bn_relu_backward and wseg_col_sums (there with C rounded up to 8) is wseg_bn_stats_workspace_bytes(M, C)
+ * = (3 * row_chunks + 3) * C floats, 16-byte aligned; -1 (and wseg_last_error) for a bad size.  row_chunks is 1 up to M = 32. */
+long wseg_bn_stats_workspace_bytes(long M, int C);
+/* The batch statistics of F.batch_norm(x, running_mean, running_var, gamma, beta, training=True, momentum, eps) (ATen batch_norm_stats +
+ * batch_norm_gather_stats_with_counts / native_batch_norm's training branch) over the M rows of every column: mean[C], invstd[C] =
+ * 1/sqrt(var + eps) with the biased variance, and where scale / shift are non-NULL the fold scale = gamma * invstd, shift = beta - mean * scale
+ * (each rounded once from f64).  running_mean / running_var (either may be NULL) become (1 - momentum) * running + momentum * stat, the variance
+ * unbiased (var * M / (M - 1)).  M < 2 is refused (torch: "Expected more than 1 value per channel").  The variance is not E[x^2] - mean^2
+ * in f32: a chunk's partial is (shift, sum (x - shift), sum (x - shift)^2) about its own first row, re-centred and merged in f64. */
+int wseg_bn_stats(const void* x, int ld, int dtype, long M, int C, const float* gamma, const float* beta, double eps, double momentum,
+                  float* mean, float* invstd, float* scale, float* shift, float* running_mean, float* running_var, void* workspace,
+                  void* stream);
+/* y = relu(z * scale[c] + shift[c]) (one fma in f32), times keep / (1 - p) when p > 0 (nn.Dropout(p): ATen native_dropout / bernoulli_), rounded
+ * once to y's dtype.  The keep bit comes from a counter hash, no mask tensor exists: with mix32 the two-round xorshift-multiply of
+ * wseg_amd/synth.py's hash_uniform, i = row * C + col, u = mix32((mix32(i) + key) mod 2^32) >> 8, keep iff u * 2^-24 >= p
+ * (synth.dropout_keep restates it on the host, bit for bit).  M * C < 2^32.  y may be z (same dtype and ld). */
+int wseg_bn_relu_drop(const void* z, int ld_z, int z_dtype, const float* scale, const float* shift, void* y, int ld_y, int y_dtype, long M,
+                      int C, float p, unsigned key, void* stream);
+/* The backward of dropout . relu . batch_norm(training=True) (ATen native_dropout_backward, threshold_backward, native_batch_norm_backward) in
+ * three launches (reduce, finish, apply): dy = s * g * [y > 0] on the STORED y (the gate covers ReLU and dropout at once; s = 1 or 1/(1 - p)),
+ * xhat = (z - mean) * invstd, s1 = sum dy, s2 = sum dy * xhat per column, dz = gamma * invstd * (dy - s1/M - xhat * s2/M) rounded once to
+ * `dtype`, the dtype of y, z and dz; g is f32 or bf16 (g_dtype).  d_beta = s1 and d_gamma = s2 are written where non-NULL.  dz may be g (same
+ * dtype and ld), not y or z. */
+int wseg_bn_relu_backward(const void* g, int ld_g, int g_dtype, const void* y, int ld_y, const void* z, int ld_z, int dtype, const float* mean,
+                          const float* invstd, const float* gamma, float s, void* dz, int ld_dz, float* d_gamma, float* d_beta, long M, int C,
+                          void* workspace, void* stream);
+/* out[c] = sum over the M rows of rows[r][c] for c < C (f32; at::sum over the pixel dims, cls_conv's bias gradient): C need not be a multiple
+ * of 8, whole chunks are read (ld >= C rounded up to 8) and the pad columns' sums are not written. */
+int wseg_col_sums(const void* rows, int ld, int dtype, long M, int C, float* out, void* workspace, void* stream);
+
 /* ---- evaluation counters (eval.py:22-52): integer pixel counts, ADDED into a caller-owned device buffer of unsigned 64-bit cells, so one
  * buffer collects a whole dataset and is read back once.  Both run on `stream` and synchronise nothing.  The ground-truth axis has
  * WSEG_EVAL_ROWS = 22 rows: 0..20 the classes, 21 = "a value in 21..254" (the evaluator counts such a pixel towards P of its predicted

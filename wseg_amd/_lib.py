@@ -631,3 +631,48 @@ def seg_ce_backward(rows, ld, label, lse, out4, gscale, d_rows, ld_d, N, fh, fw,
         raise RuntimeError(f"seg_ce_backward: lse, and contiguous device d_rows holding {N * fh * fw} rows of ld_d {ld_d} (>= {nc8})")
     _call("wseg_seg_ce_backward", _v(rows), ld, dtype_code(rows), _v(label), _v(lse), _v(out4), _v(gscale), _v(d_rows), ld_d, dtype_code(d_rows),
           N, fh, fw, H, W, n_cls)
+
+
+# ---------------------------------------------------------------------------------------------- DeepLab head, training (csrc/seg_head.hip)
+lib.wseg_bn_stats_workspace_bytes.restype = C.c_long
+
+
+def bn_stats_workspace_bytes(M, C_): return int(lib.wseg_bn_stats_workspace_bytes(C.c_long(M), C_))
+def _seg_head_extents(what, M, C_, rows=(), vecs=(), ws=None):
+    """the extents the raw pointers of a seg-head launch must cover: rows (name, tensor, ld) of M rows with C_ columns, f32 vectors (name,
+    tensor or None) of C_ elements, the workspace (the library checks dtype codes, ld, alignment and the sizes themselves)"""
+    for name, t_, ld in rows:
+        if not t_.is_cuda or t_.numel() < (M - 1) * ld + C_:
+            raise RuntimeError(f"{what}: {name} ({t_.numel()} elements on {t_.device}) does not hold {M} device rows of ld {ld} with {C_} columns")
+    for name, t_ in vecs:
+        if t_ is not None and (not t_.is_cuda or t_.dtype != torch.float32 or not t_.is_contiguous() or t_.numel() < C_):
+            raise RuntimeError(f"{what}: {name} must be a contiguous float32 device tensor of {C_} elements")
+    if ws is not None:
+        need = bn_stats_workspace_bytes(M, (C_ + 7) // 8 * 8)
+        if need < 0 or not ws.is_cuda or ws.numel() * ws.element_size() < need:
+            raise RuntimeError(f"{what}: the workspace must be a device buffer of {need} bytes ({lib.wseg_last_error().decode()})")
+def bn_stats(x, ld, M, C_, gamma, beta, eps, momentum, mean, invstd, scale, shift, running_mean, running_var, ws):
+    """wseg_bn_stats: batch mean / invstd (and the fold scale / shift, the running update: each may be None) of the C_ columns of M rows."""
+    _seg_head_extents("bn_stats", M, C_, [("x", x, ld)], [("gamma", gamma), ("beta", beta), ("mean", mean), ("invstd", invstd), ("scale", scale),
+                      ("shift", shift), ("running_mean", running_mean), ("running_var", running_var)], ws)
+    _call("wseg_bn_stats", _v(x), ld, dtype_code(x), C.c_long(M), C_, _v(gamma), _v(beta), C.c_double(eps), C.c_double(momentum), _v(mean),
+          _v(invstd), _v(scale), _v(shift), _v(running_mean), _v(running_var), _v(ws))
+def bn_relu_drop(z, ld_z, scale, shift, y, ld_y, M, C_, p=0.0, key=0):
+    """wseg_bn_relu_drop: y = relu(z * scale + shift), times keep / (1 - p) of the counter-hash mask synth.dropout_keep(M, C_, key, p) when p > 0."""
+    _seg_head_extents("bn_relu_drop", M, C_, [("z", z, ld_z), ("y", y, ld_y)], [("scale", scale), ("shift", shift)])
+    _call("wseg_bn_relu_drop", _v(z), ld_z, dtype_code(z), _v(scale), _v(shift), _v(y), ld_y, dtype_code(y), C.c_long(M), C_, _f(p),
+          C.c_uint(int(key) & 0xFFFFFFFF))
+def bn_relu_backward(g, ld_g, y, ld_y, z, ld_z, mean, invstd, gamma, s, dz, ld_dz, d_gamma, d_beta, M, C_, ws):
+    """wseg_bn_relu_backward: dz = gamma * invstd * (dy - s1/M - xhat * s2/M) with dy = s * g * [y > 0]; d_beta = s1, d_gamma = s2 (or None)."""
+    if y.dtype != z.dtype or dz.dtype != z.dtype:
+        raise TypeError(f"bn_relu_backward: y ({y.dtype}), z ({z.dtype}) and dz ({dz.dtype}) share one dtype")
+    _seg_head_extents("bn_relu_backward", M, C_, [("g", g, ld_g), ("y", y, ld_y), ("z", z, ld_z), ("dz", dz, ld_dz)],
+                      [("mean", mean), ("invstd", invstd), ("gamma", gamma), ("d_gamma", d_gamma), ("d_beta", d_beta)], ws)
+    _call("wseg_bn_relu_backward", _v(g), ld_g, dtype_code(g), _v(y), ld_y, _v(z), ld_z, dtype_code(z), _v(mean), _v(invstd), _v(gamma), _f(s),
+          _v(dz), ld_dz, _v(d_gamma), _v(d_beta), C.c_long(M), C_, _v(ws))
+def col_sums(rows, ld, M, C_, out, ws):
+    """wseg_col_sums: out[c] = the sum over the M rows of column c < C_ (f32); whole 8-column chunks are read."""
+    _seg_head_extents("col_sums", M, (C_ + 7) // 8 * 8, [("rows", rows, ld)], [], ws)
+    if not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < C_:
+        raise RuntimeError(f"col_sums: out must be a contiguous float32 device tensor of {C_} elements")
+    _call("wseg_col_sums", _v(rows), ld, dtype_code(rows), C.c_long(M), C_, _v(out), _v(ws))

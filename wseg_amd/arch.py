@@ -55,6 +55,7 @@ SEG_HEAD_CONVS = OrderedDict([
 SEG_HEAD_BNS = {"conv_fov": ("bn_fov", 512), "conv_fov2": ("bn_fov2", 512)}      # the BatchNorm registered behind a head conv
 SEG_HEAD_BIAS = ("cls_conv",)
 SEG_HEAD_DILATION = 12
+SEG_TRAIN_BN_MOM = 0.0003                         # config.py TRAIN_BN_MOM: the momentum of the head's two BatchNorms (train.py:52)
 SEG_BACKBONE_PREFIX = "backbone."
 SEG_CLS_ROWS = 24                                # cls_conv's pack and pixel rows, zero-padded: the conv launches need OC % 8 == 0
 NUM_CLASSES = 21

@@ -8,7 +8,9 @@ backbone runs through wseg_amd.engine (the contrast net's kernels and packs), th
 (Engine.run_seg_head: conv_fov is its 3x3 launch at dilation 12, both head BatchNorms folded into the epilogue, cls_conv's bias the
 epilogue's shift), the resample to the input size in csrc/seg.hip.  Inference only: in training mode `forward` raises.  Of the training
 stage the loss layer exists — wseg_amd.seg_loss.seg_cross_entropy, the cross-entropy of the resampled coarse logits and its gradient on the
-cls_conv rows (csrc/seg_loss.hip) — the training forward (BatchNorm in batch mode, dropout) and the head's backward do not yet.
+cls_conv rows (csrc/seg_loss.hip) — and the head layer: wseg_amd.seg_head, the head's training forward (BatchNorm on batch statistics, dropout)
+and its backward down to t = relu(bn7(conv6)) (csrc/seg_head.hip).  The backbone's backward from there, the data path and the trainer do not
+exist yet, so `forward` keeps refusing training mode.
 """
 import os
 
@@ -59,9 +61,9 @@ class Net(nn.Module):
         super().__init__()
         self.backbone = _Backbone()
         self.conv_fov = nn.Conv2d(4096, 512, 3, 1, padding=arch.SEG_HEAD_DILATION, dilation=arch.SEG_HEAD_DILATION, bias=False)
-        self.bn_fov = nn.BatchNorm2d(512)
+        self.bn_fov = nn.BatchNorm2d(512, momentum=arch.SEG_TRAIN_BN_MOM)
         self.conv_fov2 = nn.Conv2d(512, 512, 1, 1, padding=0, bias=False)
-        self.bn_fov2 = nn.BatchNorm2d(512)
+        self.bn_fov2 = nn.BatchNorm2d(512, momentum=arch.SEG_TRAIN_BN_MOM)
         self.dropout1 = nn.Dropout(0.5)
         self.cls_conv = nn.Conv2d(512, arch.NUM_CLASSES, 1, 1, padding=0)
         # inits of deeplabv1.py:29-36

@@ -182,6 +182,9 @@ class Engine:
         self._wt_tiles = self._wt_tiles64 = 0
         self._wt_pending = None             # (dt, mirror) until finish_packs has made the transposed packs
         self._frozen_packs = self._frozen_key = None
+        self._seg_fold_key = None           # seg_fold_key of the DeepLab head's eval folds inside _frozen_packs["bn"]
+        self.seg_stats_version = 0          # bumped by run_seg_head_train (raw kernel writes of the head BatchNorms' running statistics)
+        self._seg_train_bias = None         # run_seg_head_train: cls_conv's bias zero-padded to 24, persistent
         self._head_bufs = None
         self._fused = None                  # _fused_plan
         self._late_ev = None                # event of the late packs until the forward pass has waited for it
@@ -355,10 +358,20 @@ class Engine:
         another key is dropped (Trainer.step)."""
         net = self.net
         frozen_names = [c[0] for b in arch.BLOCKS if b[0] in arch.FROZEN_BLOCKS for c in arch.block_convs(b)]
-        return (dt, str(device)) + tuple(b._version for b in net.buffers()) + \
-            tuple(p._version for n_, p in net.named_parameters() if ".bn" in n_ or n_.startswith(("bn7", "bn_fov", "cls_conv.bias"))) + \
+        # (the DeepLab head's folds — bn_fov, bn_fov2, cls_conv's bias — have a key of their own, seg_fold_key: a training step moves them)
+        return (dt, str(device)) + tuple(b._version for n_, b in net.named_buffers() if not n_.startswith("bn_fov")) + \
+            tuple(p._version for n_, p in net.named_parameters() if ".bn" in n_ or n_.startswith("bn7")) + \
             tuple((self.conv_param(n_)._version, self.conv_param(n_).data_ptr()) for n_ in frozen_names) + \
             (net.conv1a.weight._version, net.conv1a.weight.data_ptr())
+
+    def seg_fold_key(self, device):
+        """Identity of what the DeepLab head's eval folds are computed from: the two head BatchNorms' parameters and statistics, cls_conv's bias, and
+        seg_stats_version — run_seg_head_train's kernels write the running statistics through raw pointers, which advances no tensor version.
+        Apart from frozen_key: a training step moves these three small folds, not the backbone's BN folds and b2 packs."""
+        net = self.net
+        mods = [self.bn_module(bname) for bname, _c in arch.SEG_HEAD_BNS.values()]
+        return (str(device), self.seg_stats_version, net.cls_conv.bias._version, net.cls_conv.bias.data_ptr()) + \
+            tuple(t_._version for m in mods for t_ in (m.weight, m.bias, m.running_mean, m.running_var))
 
     def ensure_packs(self, device, dt, defer_wt=False, late_stream=None):
         with self.lock:
@@ -385,17 +398,22 @@ class Engine:
                         L.pack_weights(self.conv_param(cname).detach(), wf, None, co, k * k, ci, co, ci, L.F32 if dt == L.F32X3 else dt)
                         F_["w"][cname] = self._x3(wf) if dt == L.F32X3 else wf
             F_["bn"]["bn7"] = self._bn_fold("bn7", device)
-            if getattr(net, "HEAD_KIND", "contrast") == "seg":
-                # DeepLab head (deeplabv1.py:42-49): the two head BatchNorms folded like the backbone's; cls_conv's bias as the `shift` of its launch,
-                # zero-padded to the pack's rows
-                for bname, _c in arch.SEG_HEAD_BNS.values():
-                    F_["bn"][bname] = self._bn_fold(bname, device)
-                bias = torch.zeros(arch.SEG_CLS_ROWS, device=device, dtype=torch.float32)
-                bias[:arch.NUM_CLASSES] = net.cls_conv.bias.detach().float().to(device)
-                F_["bn"]["cls_conv"] = (None, bias)
             F_["w"]["conv1a_kc"] = net.conv1a.weight.detach().to(device).float().permute(2, 3, 1, 0).reshape(27, 64).contiguous()   # [k = (ky*3+kx)*3+ic][oc] for the packed-FMA stem
             self._frozen_packs, self._frozen_key = F_, fkey
+            self._seg_fold_key = None
             self.packs = None
+        if getattr(net, "HEAD_KIND", "contrast") == "seg":
+            # DeepLab head (deeplabv1.py:42-49), eval mode: the two head BatchNorms folded like the backbone's; cls_conv's bias as the `shift` of its
+            # launch, zero-padded to the pack's rows.  Keyed apart from the frozen packs (seg_fold_key), entered into their "bn" dict in place.
+            skey = self.seg_fold_key(device)
+            if self._seg_fold_key != skey:
+                bnf = self._frozen_packs["bn"]
+                for bname, _c in arch.SEG_HEAD_BNS.values():
+                    bnf[bname] = self._bn_fold(bname, device)
+                bias = torch.zeros(arch.SEG_CLS_ROWS, device=device, dtype=torch.float32)
+                bias[:arch.NUM_CLASSES] = net.cls_conv.bias.detach().float().to(device)
+                bnf["cls_conv"] = (None, bias)
+                self._seg_fold_key = skey
         names = self.trainable_order()
         key = (dt, str(device), self.flat_w_version) + tuple(self.conv_param(n_)._version for n_ in names)
         if self.packs is not None and key == self.pack_key:
@@ -852,6 +870,65 @@ class Engine:
         rows = ps.E(M, arch.SEG_CLS_ROWS)
         ps.conv(head_conv("cls_conv", ci3, arch.SEG_CLS_ROWS, dims), f2, None, rows, shift=bn["cls_conv"][1], relu_out2=0)
         return rows
+
+    def run_seg_head_train(self, t, dims, N, drop_key, ps=None):
+        """The DeepLab-v1 head in TRAINING mode (deeplabv1.py:42-49 under train.py:52's plain nn.BatchNorm2d): the three conv launches of
+        run_seg_head, conv_fov and conv_fov2 writing their raw output z (`out`, no fold), each followed by the batch statistics (L.bn_stats, which
+        also updates the module's running statistics in place) and y = relu(z * scale + shift) (L.bn_relu_drop), the second with nn.Dropout's
+        mask of `drop_key` (synth.dropout_keep); cls_conv as in inference, its bias read from the parameter into a persistent 24-element buffer.
+        Returns (rows [M, 24], saved): saved holds z1, y1, z2, y2 and per BatchNorm stats [4, 512] f32 = mean, invstd, scale, shift."""
+        if ps is None:
+            dev = t.device
+            P = self.ensure_packs(dev, DT_OF[self.net.precision])
+            self._join_late_packs(dev)
+            ps = _Pass(self, N, dev, DT_OF[self.net.precision], P)
+        net, dev, M = self.net, t.device, ps.rows_of(dims)
+        if M * 512 >= 1 << 32:
+            raise ValueError(f"run_seg_head_train: {M} rows of 512 channels pass the dropout mask's 32-bit counter")
+        ws = torch.empty(L.bn_stats_workspace_bytes(M, 512), device=dev, dtype=torch.uint8)
+        saved, x = {}, t
+        for i, (cname, (co, ci, k)) in enumerate(list(arch.SEG_HEAD_CONVS.items())[:2], 1):
+            bn = self.bn_module(arch.SEG_HEAD_BNS[cname][0])
+            if bn.momentum is None or not bn.track_running_stats:
+                raise RuntimeError("run_seg_head_train: the head BatchNorms track running statistics with a fixed momentum")
+            z = ps.E(M, co)
+            ps.conv(head_conv(cname, ci, co, dims, k=k, dil=arch.SEG_HEAD_DILATION if k > 1 else 1), x, z)
+            stats = torch.empty(4, co, device=dev, dtype=torch.float32)
+            L.bn_stats(z, co, M, co, bn.weight.detach(), bn.bias.detach(), bn.eps, bn.momentum, stats[0], stats[1], stats[2], stats[3],
+                       bn.running_mean, bn.running_var, ws)
+            bn.num_batches_tracked += 1
+            y = ps.E(M, co)
+            L.bn_relu_drop(z, co, stats[2], stats[3], y, co, M, co, net.dropout1.p if i == 2 else 0.0, drop_key)
+            saved.update({f"z{i}": z, f"y{i}": y, f"stats{i}": stats})
+            x = y
+        self.seg_stats_version += 1
+        bias = self._seg_train_bias
+        if bias is None or bias.device != dev:
+            bias = self._seg_train_bias = torch.zeros(arch.SEG_CLS_ROWS, device=dev, dtype=torch.float32)
+        bias[:arch.NUM_CLASSES].copy_(net.cls_conv.bias.detach())
+        rows = ps.E(M, arch.SEG_CLS_ROWS)
+        ps.conv(head_conv("cls_conv", arch.SEG_HEAD_CONVS["cls_conv"][1], arch.SEG_CLS_ROWS, dims), x, None, rows, shift=bias, relu_out2=0)
+        return rows, saved
+
+    SEG_CLS_DGRAD_K = 64       # channels of the cls_conv data gradient's input: the conv launch walks K in 128-byte rows (64 bf16 / 32 f32)
+
+    def seg_head_wt(self, device):
+        """P["wt"] of the three DeepLab head convs, the data-gradient packs [IC][T][OC] in the mode's dtype (split-bf16: pre-split), made from the f32
+        masters on first use per set of packs, as aff_head_wt: inference never pays for them.  cls_conv's has SEG_CLS_DGRAD_K columns, 21 of them
+        its classes and the rest zero: its data gradient reads a gradient buffer zero-padded to that width.  Returns the current packs."""
+        dt = DT_OF[self.net.precision]
+        with self.lock:
+            P = self._ensure_packs(device, dt)
+            if "cls_conv" not in P["wt"]:
+                pdt = L.F32 if dt == L.F32X3 else dt
+                for nm, (co, ci, k) in arch.SEG_HEAD_CONVS.items():
+                    off, n = self.offsets[nm]
+                    cop = co if co % 8 == 0 else self.SEG_CLS_DGRAD_K
+                    wt = torch.zeros(ci, k * k, cop, device=device, dtype=L.TORCH_DTYPE[dt])
+                    L.pack_weights(self.flat_w[off:off + n], None, wt, co, k * k, ci, cop, ci, pdt)
+                    P["wt"][nm] = self._x3(wt) if dt == L.F32X3 else wt
+        self._join_late_packs(device)
+        return P
 
     def aff_head_wt(self, device):
         """P["wt"] of the four AffinityNet head convs, the data-gradient packs [IC][1][OC] in the mode's dtype (split-bf16: pre-split), made from the f32

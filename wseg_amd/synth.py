@@ -28,6 +28,34 @@ def hash_uniform(key, n, device="cpu"):
     return h.to(torch.float32).mul_(2.0 ** -24)
 
 
+def _mix32(h):
+    """hash_uniform's mix of an int64 tensor of 32-bit values, in place: two xorshift-multiply rounds and a final xorshift"""
+    for _ in range(2):
+        h ^= (h >> 16)
+        h *= 0x45D9F3B
+        h &= 0xFFFFFFFF
+    h ^= (h >> 16)
+    return h
+
+
+def dropout_keep(M, C, key, p=0.5, device="cpu"):
+    """bool [M, C]: the keep mask of nn.Dropout(p) as csrc/seg_head.hip's bn_relu_drop computes it from a counter, bit for bit: with i = row * C + col
+    (M * C < 2^32), u = mix32((mix32(i) + key) mod 2^32) >> 8, keep iff u * 2^-24 >= p (in float32).  The key enters BETWEEN two mixes: added to
+    the counter itself, consecutive keys give one mask shifted by an element."""
+    if M * C >= 1 << 32:
+        raise ValueError(f"dropout_keep: M * C = {M * C} passes the 32-bit counter")
+    h = _mix32(torch.arange(M * C, dtype=torch.int64, device=device))
+    h += int(key) & 0xFFFFFFFF
+    h &= 0xFFFFFFFF
+    h = _mix32(h) >> 8
+    return (h.to(torch.float32).mul_(2.0 ** -24) >= torch.tensor(p, dtype=torch.float32, device=device)).view(M, C)
+
+
+def dropout_key(seed, step):
+    """The 32-bit key of training step `step` under `seed` for dropout_keep (the DeepLab head's dropout1)"""
+    return (_key("seg.dropout1", seed) + 0x85EBCA6B * (int(step) + 1)) & 0xFFFFFFFF
+
+
 def _key(name, seed):
     return (zlib.crc32(name.encode()) + 0x9E3779B1 * (seed + 1)) & 0xFFFFFFFF
 
