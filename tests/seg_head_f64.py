@@ -20,7 +20,9 @@ chain adds + 2 wave levels <= n_t + 1; up to 3 to form the term: d = x - shift a
   scale    = gamma invstd: |gamma| invstd_bar + u |scale|;   shift = beta - mean scale: |scale| mean_bar + |mean| scale_bar + u |shift|
   running  (1 - m) r + m stat in float64, stored f32:  m stat_bar + u |result|   (running_var: stat = var M / (M - 1))
   y        relu(fma(z, scale, shift)) [* 1 / (1 - p)] from the kernel's own scale / shift: one rounding, one more for the factor: 2 u |y|,
-           stored; the dropped elements are exactly 0
+           stored; the dropped elements are exactly 0.  (p = 0.5, the head's: the factor 2 is exact and the product rounds nothing: u |y|.
+           A factor that is no power of two — p = 0.25: f32(4/3) — carries its own rounding as well: 3 u |y|, which the safety factor still
+           covers (2 x 2 u); the bar is left as it is, test_seg_head_host.py judges an f32 evaluation against it.)
   s1       = sum dy, dy = s g [y > 0] (one rounding):  D u sum |dy| + u |s1|
   s2       = sum dy xhat, xhat = (z - mean) invstd (two roundings, the fma one more):  (D + 2) u sum |dy xhat| + u |s2|
   dz       = k ((dy - m1) - xhat m2), k = gamma invstd, m1 = s1 / M, m2 = s2 / M (each stored f32):

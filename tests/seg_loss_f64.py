@@ -55,7 +55,21 @@ SHAPES = [
     ((5, 7), (29, 1), 1),
     ((13, 16), (7, 9), 1),                     # a downsample: cells with no pixel get exact zeros
     ((5, 7), (33, 47), 3),                     # image 1 entirely ignored
-]
+    ((17, 33), (131, 253), 2),                 # 66286 pixels = 259 forward workgroups: the finish adds partials t and t + 256; 33143 pixels an
+]                                              # image: one workgroup straddles the two; scales 16/130 and 32/252, both inexact in f32
+PAST_256_PARTIALS = SHAPES[-1]                 # run at 21 classes only (CLASS_CASES)
+# every (shape, n_cls) of the sweeps of tests/test_gpu_seg_loss.py and tests/test_seg_loss_host.py
+CLASS_CASES = [(s, n) for s in SHAPES for n in (21, 2) if n == 21 or s != PAST_256_PARTIALS]
+# the class counts of the other two 8-column chunk counts (NC8 = 2: 9 .. 16 classes; NC8 = 4: 25 .. 32, the maximum): the first and the last
+# of each, the last without a pad column; on an upsample and on the downsample
+NC8_COUNTS = (9, 16, 25, 32)
+NC8_SHAPES = (((5, 7), (33, 47), 1), ((13, 16), (7, 9), 1))
+
+
+def forward_workgroups(shape):
+    """workgroups of the forward launch (256 label pixels each) = partials the finish adds"""
+    (_fh, _fw), (H, W), N = shape
+    return (N * H * W + 255) // 256
 
 
 def shape_id(s):

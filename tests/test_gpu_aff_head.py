@@ -39,12 +39,19 @@ def _i(t):
 def assert_within(name, got, ref, bar):
     err = (got.double() - ref).abs()
     worst = float((err - bar).max())
-    print(f"{name}: max |err| {float(err.max()):.3e}, max bar {float(torch.as_tensor(bar).max()):.3e}, max (err - bar) {worst:.3e}")
+    ratio = float((err / torch.as_tensor(bar, dtype=torch.float64, device=err.device).clamp_min(1e-300)).max())
+    print(f"{name}: max |err| {float(err.max()):.3e}, max bar {float(torch.as_tensor(bar).max()):.3e}, max (err - bar) {worst:.3e}, "
+          f"max err / bar {ratio:.4f}")
     assert torch.isfinite(got).all() and worst <= 0.0, name
 
 
 # ------------------------------------------------------------------------------------------------ 1. the ELU-backward kernel alone
-ELU_SHAPES = [(1, 8, 8, 8, 8, 0), (35, 448, 448, 448, 448, 0), (416, 256, 448, 448, 448, 192), (1311, 64, 96, 448, 72, 0)]    # M, C, ld_g, ld_y, ld_dz, first column
+# M, C, ld_g, ld_y, ld_dz, first column.  The last: 9370 x 448 / 8 = 524720 chunks, past the 2048 x 256 threads of one launch — the second
+# trip of the grid-stride loop, on a column slice (ld 456), out of place and in place
+ELU_SHAPES = [(1, 8, 8, 8, 8, 0), (35, 448, 448, 448, 448, 0), (416, 256, 448, 448, 448, 192), (1311, 64, 96, 448, 72, 0),
+              (9370, 448, 456, 448, 456, 8)]
+ELU_STRIDES = {9370}                                           # the M whose launch takes the second trip
+ELU_GRID = 2048 * 256                                          # threads of the widest launch (csrc/aff_head.hip: at most 2048 workgroups)
 ELU_DTYPES = [(torch.float32, torch.float32, torch.float32), (torch.float32, torch.bfloat16, torch.bfloat16),
               (torch.bfloat16, torch.bfloat16, torch.bfloat16)]
 
@@ -63,6 +70,9 @@ def _round_once_bf16(exact):
 @pytest.mark.parametrize("M,C,ld_g,ld_y,ld_dz,c0", ELU_SHAPES)
 def test_elu_backward_rows(M, C, ld_g, ld_y, ld_dz, c0, dts, gscale):
     gdt, ydt, zdt = dts
+    assert (M * C // 8 > ELU_GRID) == (M in ELU_STRIDES)      # which cases stride: a later change of the grid cannot silently empty them
+    if M in ELU_STRIDES:
+        assert ld_g != C and ld_dz != C and ld_g == ld_dz      # ... on a column slice, and in place below where the dtypes agree
     gen = _gen(M + C)
     g = torch.randn(M, ld_g, generator=gen).to(gdt)
     y = F.elu(torch.randn(M, ld_y, generator=gen))
@@ -74,10 +84,11 @@ def test_elu_backward_rows(M, C, ld_g, ld_y, ld_dz, c0, dts, gscale):
     gd, yd = g.to(DEV), y.to(DEV)
     gs = None if gscale is None else torch.tensor([gscale], device=DEV)
     dz = torch.full((M, ld_dz), float("nan"), dtype=zdt, device=DEV)
-    gv, yv, zv = gd.view(-1)[c0:], yd.view(-1)[c0:], dz.view(-1)[c0:]          # a column slice: the same rows from column c0 on
+    cy = min(c0, ld_y - C)                                    # (y of ld_y = C has no column to skip: the slice of g and dz against whole rows of y)
+    gv, yv, zv = gd.view(-1)[c0:], yd.view(-1)[cy:], dz.view(-1)[c0:]          # a column slice: the same rows from column c0 on
     L.elu_backward_rows(gv, ld_g, yv, ld_y, gs, zv, ld_dz, M, C)
     got = dz.cpu()
-    g64, y64 = g.double()[:, c0:c0 + C], y.double()[:, c0:c0 + C]
+    g64, y64 = g.double()[:, c0:c0 + C], y.double()[:, cy:cy + C]
     ref, bar = H.elu_backward(g64, y64, gscale, zdt == torch.bfloat16)
     out = got[:, c0:c0 + C]
     assert torch.isfinite(out).all()

@@ -1,7 +1,9 @@
 """The DeepLab-v1 head's training path on the GPU (csrc/seg_head.hip, wseg_amd/seg_head.py, Engine.run_seg_head_train): the four kernels alone
 through _lib, the head stage by stage, the whole chain through autograd into the training loss, and inference left as it was — against the
 float64 restatement and the bars of tests/seg_head_f64.py (derived from the kernels' arithmetic, safety factor 2, never fitted to a run).
-One Net + engine per precision mode, cached at module level."""
+The kernel cases cross every size at which the kernels change path (row chunks longer than 32 rows, more than one batch of partials in the
+finish kernels, the second trip of the streaming launches: _assert_geometry states each), every option of wseg_bn_relu_drop (no dropout, a keep
+factor that is no power of two, the mixed dtype pairs) and the false-tie correction of its bf16 store on inputs aimed at it.  One Net + engine per precision mode, cached at module level."""
 import pytest
 import torch
 
@@ -33,9 +35,29 @@ def _net(mode):
 
 # ------------------------------------------------------------------------------------------------ 1. the four kernels alone
 # (M, C, ld, first column).  Row chunks (from the workspace size): 2 and 32 rows are ONE partial per column, 35 two, 416 thirteen, 1311 forty-one
-SHAPES = [(2, 8, 8, 0), (32, 16, 16, 0), (35, 512, 512, 0), (416, 512, 512, 0), (1311, 64, 96, 8)]
+# — all of 32 rows, one batch of the finish kernels.  Past 16384 rows the chunks grow (GEOMETRY): 16420 rows are 457 chunks of 36 rows with
+# a tail of 4 — four batches of 128 partials, the last one clamped — on 264 columns (no multiple of 64: idle lanes in the finish and in the
+# reduce), and 16420 x 264 / 8 chunks of 8 columns are more than the 2048 x 256 threads of a streaming launch: the second trip of the
+# grid-stride loops, out of place and in place.  31360 rows (N = 10 at 56 x 56) are 490 chunks of 64 rows, on the narrowest legal row.
+SHAPES = [(2, 8, 8, 0), (32, 16, 16, 0), (35, 512, 512, 0), (416, 512, 512, 0), (1311, 64, 96, 8), (16420, 264, 272, 8), (31360, 8, 8, 0)]
+GEOMETRY = {16420: dict(R=36, chunks=457, tail=4, depth=13), 31360: dict(R=64, chunks=490, tail=64, depth=20)}      # what the large M are there for
+STREAM_GRID = 2048 * 256                                         # threads of the widest streaming launch (sh_stream_blocks)
+FINISH_BATCH = 16 * 8                                            # partials a finish workgroup loads per batch (16 groups x SH_BATCH)
 DTYPES = [(torch.float32, torch.float32), (torch.bfloat16, torch.bfloat16), (torch.bfloat16, torch.float32)]      # (z / y / dz, g)
 KEY = 0x9E3779B1
+
+
+def _assert_geometry(M, C):
+    """the thresholds a shape crosses, from the restated constants: a later change of the kernels' constants fails here, not silently"""
+    R, chunks = H.rows_per_chunk(M), H.row_chunks(M)
+    assert (R == 32) == (M <= 16384) and chunks <= 512
+    if M in GEOMETRY:
+        geo = GEOMETRY[M]
+        assert (R, chunks, M - (chunks - 1) * R, H.depth(M)) == (geo["R"], geo["chunks"], geo["tail"], geo["depth"])
+        assert chunks > 3 * FINISH_BATCH and chunks % FINISH_BATCH != 0               # four batches, the last one partly past the end
+    else:
+        assert chunks <= FINISH_BATCH
+    return M * C // 8 > STREAM_GRID                              # the streaming launches take a second trip
 
 
 def _wide(block, ld, c0, dt):
@@ -79,6 +101,7 @@ def test_head_kernels(M, C, ld, c0, dts):
     bf = zdt == torch.bfloat16
     chunks = H.workspace_chunks(L.bn_stats_workspace_bytes(M, C), C)
     assert chunks == H.row_chunks(M) and (chunks == 1) == (M <= 32)
+    assert _assert_geometry(M, C) == (M == 16420) and (M != 16420 or (C % 64 != 0 and ld != C))
     gen = _gen(M + C)
     z = torch.randn(M, C, generator=gen)
     z[:, 0] += 64.0                                             # mean = 64 std: the cancellation case
@@ -129,6 +152,131 @@ def test_head_kernels(M, C, ld, c0, dts):
             assert torch.isnan(b.cpu()[cols]).all()
             a, b = a[:, c0:c0 + C], b[:, c0:c0 + C]
         assert torch.equal(_i(a), _i(b)), k
+
+
+# wseg_bn_relu_drop alone: every (z, y) dtype pair at p = 0 (the launch after bn_fov: no dropout), 0.25 (a keep factor that is no power of two)
+# and 0.5, on a small column slice of several workgroups and on the shape whose launch strides
+DROP_SHAPES = [(1311, 64, 96, 8), (16420, 264, 272, 8)]
+DROP_DTYPES = [(torch.float32, torch.float32), (torch.bfloat16, torch.bfloat16), (torch.float32, torch.bfloat16), (torch.bfloat16, torch.float32)]   # (z, y)
+
+
+def _drop_once(z, zdt, ydt, scale, shift, M, C, ld, c0, p, key):
+    _zw, zv = _wide(z, ld, c0, zdt)
+    yw, yv = _wide(torch.full((M, C), float("nan")), ld, c0, ydt)
+    L.bn_relu_drop(zv, ld, scale, shift, yv, ld, M, C, p, key)
+    return yw
+
+
+@pytest.mark.parametrize("p", [0.0, 0.25, 0.5])
+@pytest.mark.parametrize("dts", DROP_DTYPES, ids=lambda d: "-".join(str(x).replace("torch.", "") for x in d))
+@pytest.mark.parametrize("M,C,ld,c0", DROP_SHAPES)
+def test_bn_relu_drop_options(M, C, ld, c0, dts, p):
+    zdt, ydt = dts
+    bf = ydt == torch.bfloat16
+    large = _assert_geometry(M, C)
+    assert large == (M == 16420)
+    gen = _gen(M + C + 1)
+    z = torch.randn(M, C, generator=gen).to(zdt).float()
+    scale, shift = _vec(C, torch.rand(C, generator=gen) + 0.5), _vec(C, torch.rand(C, generator=gen) - 0.5)
+    shift[2] = -100.0                                           # y is zero in every row of column 2
+    yw = _drop_once(z, zdt, ydt, scale, shift, M, C, ld, c0, p, KEY)
+    cols = torch.ones(M, ld, dtype=torch.bool)
+    cols[:, c0:c0 + C] = False
+    assert torch.isnan(yw.cpu()[cols]).all()                    # nothing outside the C columns is written
+    y = yw[:, c0:c0 + C]
+    z64, sc64, sh64 = z.double().to(DEV), scale[:C].double(), shift[:C].double()
+    keep = synth.dropout_keep(M, C, KEY, p, device=DEV) if p > 0 else None
+    assert_within(f"y (p = {p})", y, *H.bn_relu_drop(z64, sc64, sh64, keep, p, bf))
+    pre = torch.relu(z64 * sc64 + sh64)
+    assert bool((y[:, 2] == 0).all()) and 0.3 < float((pre > 0).double().mean()) < 0.7
+    other = _drop_once(z, zdt, ydt, scale, shift, M, C, ld, c0, p, KEY + 1)[:, c0:c0 + C]
+    if p == 0.0:                                                # relu(fma(z, scale, shift)) rounded once; no element dropped, the key unused
+        once = _round_once_bf16(pre) if bf else pre.float()
+        assert torch.equal(_i(y), _i(once)) and torch.equal(_i(other), _i(y))
+        return
+    assert bool((y[~keep] == 0).all()) and bool((y[keep & (pre.float() > 0)] > 0).all())     # the dropped elements: exactly the mask's zeros
+    assert not torch.equal(_i(other), _i(y))
+    share = float(keep.double().mean())
+    if large:
+        assert abs(share - (1.0 - p)) <= 0.01, share            # (4.3 M elements: 0.01 is 48 standard deviations)
+    if p == 0.5:                                                # the factor 2 is exact: the kept elements are 2 relu(.) rounded once
+        once = _round_once_bf16(2.0 * pre) if bf else (2.0 * pre).float()
+        assert torch.equal(_i(y[keep]), _i(once[keep]))
+    # (p = 0.25: the f32 factor 4/3 and its product round again, "rounded once" does not hold and is not asserted: the bar above is the test)
+
+
+# ---- the false-tie correction (sh_off_the_false_tie), aimed at.  fmaf(z, a, b) is ONE rounding to f32; the bf16 store rounds again.  Where the
+# f32 value ends in 0x8000 — exactly between two bf16 values — while the exact z a + b does not, the second rounding alone would go to the even
+# neighbour whatever side the exact value is on.  a0 / a1 = 1 + 2^-8 / 1 + 2^-7 + 2^-8 are such patterns with an even / odd bf16 below;
+# b = +-2^-30 is below half an f32 ulp of the product: it decides the side and leaves the f32 pattern.  2^-60 does the same and vanishes in
+# float64 too (the kernel's residual branch): the oracle is exact rational arithmetic, and equals the float64 expression wherever that is exact.
+_A0, _A1, _T, _E = 1.0 + 2.0 ** -8, 1.0 + 2.0 ** -7 + 2.0 ** -8, 2.0 ** -30, 2.0 ** -60
+# (z, scale, shift, expected bf16 bits or None, lands on the tie pattern)
+TIES = [
+    (1.0, _A0, _T, 0x3F81, True), (1.0, _A0, -_T, 0x3F80, True), (1.0, _A0, 0.0, 0x3F80, True),           # false ties, and the true tie: even
+    (1.0, _A1, _T, 0x3F82, True), (1.0, _A1, -_T, 0x3F81, True), (1.0, _A1, 0.0, 0x3F82, True),           # the odd neighbour below
+    (1.0, _A0, _E, 0x3F81, True), (1.0, _A0, -_E, 0x3F80, True), (1.0, _A1, -_E, 0x3F81, True), (1.0, _A1, _E, 0x3F82, True),
+    (-1.0, -_A0, _T, 0x3F81, True), (-1.0, -_A0, -_T, 0x3F80, True), (-1.0, -_A1, -_T, 0x3F81, True),     # a positive result of negative operands
+    (1.0, -_A0, _T, 0x0000, True), (1.0, -_A0, -_T, 0x0000, True), (-1.0, _A1, 0.0, 0x0000, True),        # a negative pre-activation: +0
+    (2.0, _A0, _T, 0x4001, True), (0.5, _A1, -_T, 0x3F01, True), (4.0, _A1, 0.0, 0x4082, True),           # other binades
+    (1.0, 1.0, _T, 0x3F80, False), (1.0, _A0 + 2.0 ** -20, 0.0, 0x3F81, False),                           # no tie pattern: the correction stays out
+    (_A0, 1.0, _T, 0x3F81, True), (_A0, 1.0, -_T, 0x3F80, True), (_A1, 1.0, 0.0, 0x3F82, True), (_A0, 2.0, -_T, 0x4000, True),   # f32 z carries it
+    (_A1, 1.0, -_T, 0x3F81, True), (_A0, -1.0, _T, 0x0000, True),
+]
+TIES_BF16_Z = [t_ for t_ in TIES if t_[0] in (1.0, -1.0, 2.0, 0.5, 4.0)]
+
+
+def _bf16_bits(x):
+    """the bf16 bit pattern of the non-negative rational x (a normal number or 0), rounded ONCE, to nearest, ties to even"""
+    from fractions import Fraction
+    if x == 0:
+        return 0
+    e = 0
+    while Fraction(2) ** (e + 1) <= x:
+        e += 1
+    while Fraction(2) ** e > x:
+        e -= 1
+    m = x / Fraction(2) ** (e - 7)                               # in [128, 256): 8 significant bits before the point
+    q, rem = int(m), m - int(m)
+    q += 1 if rem > Fraction(1, 2) or (rem == Fraction(1, 2) and q % 2 == 1) else 0
+    return ((e + 127) << 7) + (q - 128)                          # (q = 256 carries into the exponent by itself)
+
+
+@pytest.mark.parametrize("zdt", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_bn_relu_drop_false_ties(zdt):
+    from fractions import Fraction
+    ties = TIES if zdt == torch.float32 else TIES_BF16_Z
+    n, M = len(ties), 32                                         # one row block; every row holds every case (z is constant down a column)
+    C = (n + 7) // 8 * 8
+    assert M * C // 8 <= 256
+    zc, sc, sh = torch.ones(C), torch.ones(C), torch.zeros(C)
+    zc[:n], sc[:n], sh[:n] = (torch.tensor([t_[j] for t_ in ties], dtype=torch.float64).float() for j in range(3))
+    assert torch.equal(zc.to(zdt).float(), zc) and [float(v) for v in sc[:n]] == [t_[1] for t_ in ties]       # the operands are exact
+    assert _i(sc[:1])[0] == 0x3F808000 and 0x3F818000 in _i(sc[:n]).tolist()
+    exact = [Fraction(t_[0]) * Fraction(t_[1]) + Fraction(t_[2]) for t_ in ties]
+    r32 = torch.tensor([float(v) for v in exact], dtype=torch.float64).float()          # fmaf's result (these double roundings are exact or far off a tie)
+    on_tie = [(b & 0xFFFF) == 0x8000 for b in _i(r32).tolist()]
+    assert on_tie == [t_[4] for t_ in ties] and sum(e_ != Fraction(float(r)) for e_, r, t_ in zip(exact, r32, ties) if t_[4]) >= 12
+    z = zc[None, :].expand(M, C).contiguous()
+    scale, shift = _vec(C, sc), _vec(C, sh)
+    z64 = z.double().to(DEV)
+    for p, factor in ((0.0, 1), (0.5, 2)):
+        want = torch.tensor([_bf16_bits(max(v, Fraction(0)) * factor) for v in exact], dtype=torch.int32)
+        if p == 0.0:
+            assert want.tolist() == [t_[3] for t_ in ties]
+        yw = _drop_once(z, zdt, torch.bfloat16, scale, shift, M, C, C, 0, p, KEY)
+        got = _i(yw).cpu().to(torch.int32) & 0xFFFF
+        keep = synth.dropout_keep(M, C, KEY, p) if p > 0 else torch.ones(M, C, dtype=torch.bool)
+        assert bool(keep[:, :n].any(0).all()) and bool((got[~keep] == 0).all())         # every case is kept in some row
+        rows_want = want[None, :].expand(M, n)
+        bad = (got[:, :n] != rows_want) & keep[:, :n]
+        assert not bool(bad.any()), (p, [(ties[c], hex(int(got[r, c]))) for r, c in bad.nonzero().tolist()[:8]])
+        # the float64 expression rounded once is the same oracle wherever float64 holds the sum exactly (all but the 2^-60 shifts)
+        f64 = factor * torch.relu(z64 * scale[:C].double() + shift[:C].double())
+        once = (_i(_round_once_bf16(f64)).cpu().to(torch.int32) & 0xFFFF)[:, :n]
+        exact64 = torch.tensor([abs(t_[2]) != _E for t_ in ties])
+        assert torch.equal(once[:, exact64], rows_want[:, exact64])
+        assert torch.equal(got[:, :n][:, exact64][keep[:, :n][:, exact64]], once[:, exact64][keep[:, :n][:, exact64]])
 
 
 def test_col_sums_of_the_cls_gradient_rows():
@@ -232,6 +380,75 @@ def test_head_stage_by_stage(mode, N, h, w):
         assert_within("dW_fov" + tag, eng.grad_view("conv_fov").reshape(512, 4096 * 9), *H.wgrad(X0, d(cap["dz1"]), mode))
         assert_within("d_t" + tag, d_t, *H.dgrad3(d(cap["dz1"]), W["conv_fov"], N, h, w, mode, *((d(scale7), d(t)) if epi1 else ())))
         assert set(cap["plans"]) == {"cls_conv", "conv_fov2", "conv_fov"}
+    _reset_grads(net, eng)
+
+
+def test_head_stages_past_16384_rows_bf16():
+    """N = 1, 129 x 128 = 16512 rows in bf16: the smallest map whose column reductions run 36-row chunks (459 of them, a tail of 24) — through the
+    engine path's own workspace, d_pad and in-place backward, which the kernel tests above do not touch.  Every launch but the two of K = 36864
+    is held to its bar from the path's own upstream tensors, as in test_head_stage_by_stage.  The dilation-12 conv_fov launches (forward, data
+    and weight gradient) are only required to be finite here: their unfolded float64 operand would be 5 GB, and tests/test_gpu_seg_head_conv.py
+    and tests/test_gpu_seg_head_bwd_conv.py hold those launches on every tile family.  The families the planner chose are printed."""
+    from wseg_amd.seg_head import _conv
+    mode, N, h, w = "bf16", 1, 129, 128
+    net, bf, M = _net(mode), True, N * h * w
+    assert M > 16384 >= 128 * 128                                                                          # the first map past the threshold
+    assert (H.rows_per_chunk(M), H.row_chunks(M), M - 458 * 36, H.depth(M)) == (36, 459, 24, 13)
+    assert M * 512 // 8 > STREAM_GRID                                                                      # the streaming launches stride
+    key = synth.dropout_key(3, h)
+    t = torch.relu(torch.randn(M, 4096, generator=torch.Generator(device=DEV).manual_seed(M), device=DEV)).to(TDT[mode])
+    bns = (net.bn_fov, net.bn_fov2)
+    before = [(b.running_mean.double().clone(), b.running_var.double().clone(), int(b.num_batches_tracked)) for b in bns]
+    rows, ctx = seg_head_forward(net, t, N, h, w, key)
+    eng = ctx["eng"]
+    W = {k: v.to(DEV) for k, v in H.weights64(net, mode).items()}
+    d = lambda x: x.double()                                                    # noqa: E731
+    keep = synth.dropout_keep(M, 512, key, P, device=DEV)
+    assert bool(torch.isfinite(ctx["z1"]).all())                                # conv_fov forward: finite only (see above)
+    assert_within("z2", ctx["z2"], *H.conv(d(ctx["y1"]), W["conv_fov2"], mode))
+    for i, bn in enumerate(bns, 1):
+        st = H.bn_stats(d(ctx[f"z{i}"]), d(bn.weight.detach()), d(bn.bias.detach()), bn.eps, bn.momentum, before[i - 1][0], before[i - 1][1])
+        for j, k in enumerate(("mean", "invstd", "scale", "shift")):
+            assert_within(f"{k}{i}", ctx[f"stats{i}"][j], *st[k])
+        assert_within(f"running_mean{i}", bn.running_mean, *st["running_mean"])
+        assert_within(f"running_var{i}", bn.running_var, *st["running_var"])
+        assert int(bn.num_batches_tracked) == before[i - 1][2] + 1
+        assert_within(f"y{i}", ctx[f"y{i}"], *H.bn_relu_drop(d(ctx[f"z{i}"]), d(ctx[f"stats{i}"][2]), d(ctx[f"stats{i}"][3]), keep if i == 2 else None, P, bf))
+    assert bool((ctx["y2"][~keep] == 0).all())
+    W3 = torch.zeros(24, 512, dtype=torch.float64, device=DEV)
+    W3[:21] = W["cls_conv"]
+    bias = torch.zeros(24, dtype=torch.float64, device=DEV)
+    bias[:21] = d(net.cls_conv.bias.detach())
+    assert_within("rows", rows, *H.conv(d(ctx["y2"]), W3, mode, bias))
+    assert bool((rows[:, 21:] == 0).all())
+
+    d_rows = torch.zeros(M, 24, device=DEV)
+    d_rows[:, :21] = torch.randn(M, 21, generator=torch.Generator(device=DEV).manual_seed(M + 1), device=DEV) / M
+    _reset_grads(net, eng)
+    cap = {}
+    d_t = seg_head_backward(ctx, d_rows, capture=cap)
+    dp = d(cap["d_pad"])[:, :21]
+    assert bool((cap["d_pad"][:, 21:] == 0).all())
+    assert_within("d_bias", net.cls_conv.bias.grad, *H.col_sums(d(d_rows)[:, :21]))
+    assert_within("dW_cls", eng.grad_view("cls_conv").reshape(21, 512), *H.wgrad(d(ctx["y2"]), dp, mode))
+    assert_within("d_y2", cap["d_y2"], *H.dgrad(dp, W["cls_conv"], mode))
+    b2 = H.bn_relu_backward(d(cap["d_y2"]), d(ctx["y2"]), d(ctx["z2"]), d(ctx["mean2"]), d(ctx["invstd2"]), d(net.bn_fov2.weight.detach()), 2.0, bf)
+    assert_within("dz2", cap["dz2"], *b2["dz"])
+    assert_within("d_beta2", net.bn_fov2.bias.grad, *b2["s1"])
+    assert_within("d_gamma2", net.bn_fov2.weight.grad, *b2["s2"])
+    assert_within("dW_fov2", eng.grad_view("conv_fov2").reshape(512, 512), *H.wgrad(d(ctx["y1"]), d(cap["dz2"]), mode))
+    assert_within("d_y1", cap["d_y1"], *H.dgrad(d(cap["dz2"]), W["conv_fov2"], mode))
+    b1 = H.bn_relu_backward(d(cap["d_y1"]), d(ctx["y1"]), d(ctx["z1"]), d(ctx["mean1"]), d(ctx["invstd1"]), d(net.bn_fov.weight.detach()), 1.0, bf)
+    assert_within("dz1", cap["dz1"], *b1["dz"])
+    assert_within("d_beta1", net.bn_fov.bias.grad, *b1["s1"])
+    assert_within("d_gamma1", net.bn_fov.weight.grad, *b1["s2"])
+    dW_fov = eng.grad_view("conv_fov")
+    assert bool(torch.isfinite(dW_fov).all()) and bool(torch.isfinite(d_t).all()) and float(dW_fov.abs().max()) > 0 and float(d_t.abs().max()) > 0
+    assert set(cap["plans"]) == {"cls_conv", "conv_fov2", "conv_fov"}
+    launches = backward_launches(N, h, w, L.BF16)
+    for name in H.CONVS:
+        fwd = L.conv_plan(dtype=L.BF16, **_conv(name, [(h, w)], arch.SEG_CLS_ROWS if name == "cls_conv" else None).fwd_kw(N))
+        print(f"{name}: forward geometry {fwd}; data gradient {cap['plans'][name]}; weight gradient {L.wgrad_plan(**launches['wgrad_' + name])}")
     _reset_grads(net, eng)
 
 

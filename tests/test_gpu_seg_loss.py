@@ -2,7 +2,9 @@
 tests/seg_loss_f64.py (from the arithmetic, safety factor 2, never fitted to a run; judged on the CPU by tests/test_seg_loss_host.py).
 
 The kernels run on the engine layout — pixel rows of ld 24 with 1e30 in the pad columns, which must never reach a result — for f32 and bf16
-rows (bf16 rows are read exactly: the float64 side gets the same values), 21 and 2 classes, over every shape of seg_loss_f64.SHAPES.  The
+rows (bf16 rows are read exactly: the float64 side gets the same values), 21 and 2 classes, over every shape of seg_loss_f64.SHAPES (the
+shape whose forward launch has more than 256 workgroups — the finish kernel's second trip — at 21 classes only), and for 9, 16, 25 and 32
+classes (two and four 8-class chunks, the kernels' other instantiations) on rows of ld = the chunks and 8 columns wider.  The
 two counts of out4 are EQUAL to the float64 counts; the loss, the per-pixel log-sum-exp and every element of the gradient lie within their
 bars (a coarse cell no valid pixel touches has the bar 0: exact zeros); no pixel is excluded.  The named cases pin what no bar expresses:
 torch's answer on an all-ignored batch, out-of-range labels, exact power-of-two gscale, the loss-only call, run-to-run bits, the batch
@@ -35,12 +37,12 @@ def _grad_of(d, coarse):
     return d[:, :C].float().view(N, fh, fw, C).permute(0, 3, 1, 2)
 
 
-def _run(coarse, label, dtype, d_dtype=torch.float32, ld_d=None, gscale=None):
-    """(out4, lse, d_rows) on the host: forward and backward of the engine-layout entry points; d_rows starts as SENTINEL everywhere"""
+def _run(coarse, label, dtype, d_dtype=torch.float32, ld_d=None, gscale=None, ld=LD):
+    """(out4, lse, d_rows) on the host: forward and backward of the engine-layout entry points on rows of `ld`; d_rows starts as SENTINEL everywhere"""
     from wseg_amd.seg_loss import seg_ce_rows, seg_ce_rows_backward
     N, C, fh, fw = coarse.shape
     H, W = label.shape[1:]
-    out4, ctx = seg_ce_rows(_rows(coarse, dtype), LD, label.cuda(), N, fh, fw, H, W, C)
+    out4, ctx = seg_ce_rows(_rows(coarse, dtype, ld), ld, label.cuda(), N, fh, fw, H, W, C)
     ld_d = ld_d or (C + 7) // 8 * 8
     d = torch.full((N * fh * fw, ld_d), SENTINEL, dtype=d_dtype, device="cuda")
     seg_ce_rows_backward(ctx, None if gscale is None else torch.tensor([gscale], device="cuda"), out=d, ld_d=ld_d)
@@ -61,25 +63,55 @@ def _check(got, ref, coarse, what, **kw):
     assert all(ok for ok, _r in verdict.values()), (what, verdict)
 
 
-@pytest.mark.parametrize("dt", list(DTYPES))
-@pytest.mark.parametrize("n_cls", [21, 2])
-@pytest.mark.parametrize("shape", S.SHAPES, ids=S.shape_id)
-def test_kernels_against_float64(shape, n_cls, dt):
+def _sweep_case(shape, n_cls, dt, ld=LD):
+    """one case of the sweep on rows of `ld`; returns what the f32 d_rows run gave"""
     coarse, label, ref = _case(shape, n_cls, dt)
     nc8 = (n_cls + 7) // 8 * 8
-    out4, lse, d = _run(coarse, label, DTYPES[dt])
+    out4, lse, d = _run(coarse, label, DTYPES[dt], ld=ld)
     assert float(out4[1]) == float(ref["count"]) and float(out4[3]) == float(ref["oor"]) == 0.0         # integer counts: equal, not close
     assert S.within(out4[2], ref["nll_sum"], S.nll_sum_bar(ref, coarse))
-    _check(dict(loss=out4[0], lse=lse, grad=_grad_of(d, coarse)), ref, coarse, f"{S.shape_id(shape)} n_cls {n_cls} {dt} rows, f32 d_rows")
-    assert bool((d[:, n_cls:nc8] == 0).all())                                                          # the pad columns of the 8-chunk: zeros
-    # bf16 d_rows: the same f32 sums rounded once; ld_d = 32: the columns past the chunk keep what they held
-    out4_b, _lse, d_b = _run(coarse, label, DTYPES[dt], d_dtype=torch.bfloat16, ld_d=32)
+    _check(dict(loss=out4[0], lse=lse, grad=_grad_of(d, coarse)), ref, coarse, f"{S.shape_id(shape)} n_cls {n_cls} {dt} rows of ld {ld}, f32 d_rows")
+    assert d.shape[1] == nc8 and bool((d[:, n_cls:nc8] == 0).all())                                    # the pad columns of the 8-chunk: zeros
+    assert (d[:, n_cls:nc8].numel() == 0) == (n_cls % 8 == 0)                                          # (a whole chunk of classes has no pad column)
+    # bf16 d_rows: the same f32 sums rounded once; ld_d = 32 (40 for four chunks): the columns past the chunks keep what they held
+    ld_w = max(32, nc8 + 8)
+    out4_b, _lse, d_b = _run(coarse, label, DTYPES[dt], d_dtype=torch.bfloat16, ld_d=ld_w, ld=ld)
     assert torch.equal(out4_b, out4)
     assert torch.equal(d_b[:, :nc8], d.bfloat16())                                                     # ONE rounding of the f32 result
     _check(dict(loss=out4_b[0], grad=_grad_of(d_b, coarse)), ref, coarse, "   bf16 d_rows", grad_store_bf16=True)
-    assert bool((d_b[:, n_cls:nc8] == 0).all()) and bool((d_b[:, nc8:] == SENTINEL).all())
-    _o, _l, d_w = _run(coarse, label, DTYPES[dt], ld_d=32)
+    assert bool((d_b[:, n_cls:nc8] == 0).all()) and bool((d_b[:, nc8:] == SENTINEL).all()) and d_b.shape[1] == ld_w > nc8
+    _o, _l, d_w = _run(coarse, label, DTYPES[dt], ld_d=ld_w, ld=ld)
     assert torch.equal(d_w[:, :nc8], d) and bool((d_w[:, nc8:] == SENTINEL).all())
+    return out4, lse, d
+
+
+SWEEP = [pytest.param(s, n, id=f"{S.shape_id(s)}-{n}") for s, n in S.CLASS_CASES]
+
+
+@pytest.mark.parametrize("dt", list(DTYPES))
+@pytest.mark.parametrize("shape,n_cls", SWEEP)
+def test_kernels_against_float64(shape, n_cls, dt):
+    (_fh, _fw), (H, W), N = shape
+    if shape == S.PAST_256_PARTIALS:                               # what the case is there for: the finish kernel's second trip, an image
+        assert S.forward_workgroups(shape) > 256 and (H * W) % 256 != 0 and N == 2 and n_cls == 21     # boundary inside a workgroup
+    else:
+        assert S.forward_workgroups(shape) <= 256
+    _sweep_case(shape, n_cls, dt)
+
+
+@pytest.mark.parametrize("dt", list(DTYPES))
+@pytest.mark.parametrize("n_cls", S.NC8_COUNTS)
+@pytest.mark.parametrize("shape", S.NC8_SHAPES, ids=S.shape_id)
+def test_every_class_chunk_count(shape, n_cls, dt):
+    """the kernels are instantiated per number of 8-class chunks (1 .. 4): 9 / 16 classes run two, 25 / 32 four (21 runs three, 2 and 8 one).
+    Rows of ld = the chunks themselves (16 and 32 classes: not one pad column anywhere), and rows 8 columns wider with the poison behind
+    the chunks: the same bits."""
+    nc8 = (n_cls + 7) // 8 * 8
+    assert nc8 // 8 == {9: 2, 16: 2, 25: 4, 32: 4}[n_cls] and n_cls <= 32
+    tight = _sweep_case(shape, n_cls, dt, ld=nc8)
+    coarse, label, _ref = _case(shape, n_cls, dt)
+    wide = _run(coarse, label, DTYPES[dt], ld=nc8 + 8)
+    assert all(torch.equal(a, b) for a, b in zip(tight, wide))
 
 
 def _torch_f64(coarse, label):
@@ -114,6 +146,27 @@ def test_out_of_range_labels_are_counted_and_ignored():
     assert float(out4[3]) == n_bad > 0 and float(out4_c[3]) == 0.0
     assert torch.equal(out4[:3], out4_c[:3]) and torch.equal(lse, lse_c) and torch.equal(d, d_c)        # they contribute nothing
     assert float(out4[1]) == float((clean < 21).sum())
+
+
+def test_out_of_range_labels_at_nine_classes():
+    """the same with 9 classes on rows of ld 16: the values 9 .. 15 are columns of the second chunk (zeros in the engine's rows, the poison here)
+    and must be ignored like 254, never read as a class"""
+    coarse, label, ref = _case(((5, 7), (33, 47), 1), 9, "f32")
+    bad = label.clone()
+    g = torch.Generator().manual_seed(6)
+    where = torch.rand(label.shape, generator=g) < 0.1
+    bad[where] = torch.randint(9, 255, (int(where.sum()),), generator=g, dtype=torch.int64).to(torch.uint8)
+    bad[0, 0, 0], bad[0, 0, 1], bad[0, -1, -2], bad[0, -1, -1] = 9, 15, 16, 254      # both ends of the range, both sides of the chunk's end
+    clean = torch.where(bad >= 9, torch.full_like(bad, 255), bad)
+    n_bad = int(((bad >= 9) & (bad != 255)).sum())
+    out4, lse, d = _run(coarse, bad, torch.float32, ld=16)
+    out4_c, lse_c, d_c = _run(coarse, clean, torch.float32, ld=16)
+    assert float(out4[3]) == n_bad > 0 and float(out4_c[3]) == 0.0
+    assert torch.equal(out4[:3], out4_c[:3]) and torch.equal(lse, lse_c) and torch.equal(d, d_c)        # they contribute nothing
+    assert float(out4[1]) == float((clean < 9).sum()) < float(ref["count"])
+    ref_c = S.restate(coarse, clean)                                                                   # and what is left is the loss of the clean map
+    _check(dict(loss=out4[0], lse=lse, grad=_grad_of(d, coarse)), ref_c, coarse, "9 classes, out-of-range labels")
+    assert bool((d[:, 9:] == 0).all())
 
 
 def test_gscale_is_exact_for_powers_of_two():
@@ -164,14 +217,16 @@ def test_image_one_of_a_batch_equals_the_image_alone():
 @pytest.mark.parametrize("label_dtype", [torch.uint8, torch.int64])
 @pytest.mark.parametrize("channels_last", [False, True])
 @pytest.mark.parametrize("dt", list(DTYPES))
-@pytest.mark.parametrize("n_cls", [21, 8])                           # 8: channels_last rows are consumed in place; 21: packed into rows of ld 24
-def test_autograd_wrapper(n_cls, dt, channels_last, label_dtype):
+@pytest.mark.parametrize("n_cls", [21, 8, 16, 32])                   # 8, 16, 32 (one, two, four whole chunks): channels_last rows are consumed
+def test_autograd_wrapper(n_cls, dt, channels_last, label_dtype):    # in place; 21: packed into rows of ld 24
     from wseg_amd.seg_loss import seg_cross_entropy
     shape = ((5, 7), (33, 47), 3)
     coarse, label, ref = _case(shape, n_cls, dt)
     fmt = torch.channels_last if channels_last else torch.contiguous_format
     x = coarse.to(DTYPES[dt]).cuda().contiguous(memory_format=fmt).requires_grad_()
     loss, stats = seg_cross_entropy(x, label.to(label_dtype).cuda())
+    if channels_last and n_cls % 8 == 0:                             # no copy: the loss's rows ARE x's storage
+        assert loss.grad_fn.saved["rows"].data_ptr() == x.data_ptr()
     (loss * 0.5).backward()
     assert x.grad.dtype == DTYPES[dt] and x.grad.shape == x.shape and x.grad.is_contiguous(memory_format=fmt)
     assert not stats.requires_grad and float(stats[0]) == float(loss.detach()) and float(stats[1]) == float(ref["count"]) and float(stats[3]) == 0.0

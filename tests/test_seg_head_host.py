@@ -1,6 +1,8 @@
 """tests/seg_head_f64.py on the CPU: the stage restatements chained equal torch's float64 autograd of the reference's lines (output, d_t, every
 parameter gradient, the running statistics of nn.BatchNorm2d(512, momentum=0.0003) after one step); a float32 evaluation of the same chain
-passes every bar and planted defects fail one; the counter-hash dropout mask of synth.dropout_keep is balanced and its keys are independent;
+passes every bar and planted defects fail one — also at 16420 and 31360 rows, where the row chunks are longer than 32 rows and the finish
+kernels load more than one batch of partials (a miscounted tail chunk, a dropped batch and a reduce that disagrees with the finish about the
+chunk length are planted there), and with the keep factor 4/3 of p = 0.25; the counter-hash dropout mask of synth.dropout_keep is balanced and its keys are independent;
 the refusals of wseg_amd.seg_head."""
 import math
 
@@ -29,17 +31,23 @@ def _problem():
     return p
 
 
-def _stats32(x, gamma, beta, rm, rv):
-    """wseg_bn_stats's arithmetic on f32 rows: per chunk the f32 sums about the chunk's first row, the finish in float64, outputs rounded to f32"""
+def _stats32(x, gamma, beta, rm, rv, defect=None):
+    """wseg_bn_stats's arithmetic on f32 rows: per chunk the f32 sums about the chunk's first row, the finish in float64, outputs rounded to f32.
+    defect: a planted fault of the large geometries (test_planted_size_defects_fail) — "tail_is_full": the finish counts the short last chunk as
+    R rows; "first_batch_only": the finish adds the first 128 chunks and stops; "reduce_in_32_rows": the reduce sums 32 rows from each chunk's
+    first row while the finish (and the chunks' first rows) follow R"""
     R = H.rows_per_chunk(x.shape[0])
     g = x[0].double()
     S1, S2 = torch.zeros_like(g), torch.zeros_like(g)
-    for r0 in range(0, x.shape[0], R):
+    for k, r0 in enumerate(range(0, x.shape[0], R)):
+        if defect == "first_batch_only" and k >= 128:
+            break
         blk = x[r0:r0 + R]
-        d = blk - blk[0]
+        n = R if defect == "tail_is_full" else blk.shape[0]
+        d = (blk[:32] if defect == "reduce_in_32_rows" else blk) - blk[0]
         s1, s2, dk = d.sum(0).double(), (d * d).sum(0).double(), blk[0].double() - g
-        S1 += s1 + blk.shape[0] * dk
-        S2 += s2 + 2 * dk * s1 + blk.shape[0] * dk * dk
+        S1 += s1 + n * dk
+        S2 += s2 + 2 * dk * s1 + n * dk * dk
     m = x.shape[0]
     mean = g + S1 / m
     var = ((S2 - S1 * S1 / m) / m).clamp_min(0)
@@ -229,6 +237,112 @@ def test_backward_defects_fail():
     for kw in (dict(use_s1=False), dict(use_s2=False), dict(s=1.0), dict(gate=pre)):
         assert not H.inside(dz(**kw)[0], *ref["dz"])[0], kw
     assert not H.inside(dz(s=1.0)[1], *ref["s1"])[0] and not H.inside(dz(gate=pre)[2], *ref["s2"])[0]
+
+
+# ------------------------------------------------------------------------------------------------------------------ past 16384 rows
+# 16420 rows: 457 chunks of 36 rows, the last of 4 — four batches of 128 partials in the finish, depth 13.  31360 rows (N = 10 at 56 x 56):
+# 490 chunks of 64 rows, depth 20.  The GPU cases of tests/test_gpu_seg_head.py run these geometries; here the bars are judged at them.
+BIG = {16420: (36, 457, 4, 13), 31360: (64, 490, 64, 20)}
+
+
+def _big_rows(m_, seed):
+    """[m_, 16] f32 rows of unit spread: column 0 has mean 64 std, column 1 is constant"""
+    x = _rand((m_, 16), seed, 3 ** 0.5)
+    x[:, 0] += 64.0
+    x[:, 1] = 0.375
+    return x.float()
+
+
+def _bwd32(g, y, z, st, gamma, s, chunks=None):
+    """wseg_bn_relu_backward's arithmetic in f32: per chunk the f32 sums of dy and dy * xhat, added in float64, m1 / m2 / k rounded to f32, dz in
+    f32.  chunks: add only the first so many partials (a planted fault)"""
+    m_, R = z.shape[0], H.rows_per_chunk(z.shape[0])
+    dy = s * g * (y > 0)
+    xhat = (z - st["mean"]) * st["invstd"]
+    t2 = dy * xhat
+    S1, S2 = torch.zeros(z.shape[1], dtype=torch.float64), torch.zeros(z.shape[1], dtype=torch.float64)
+    for k, r0 in enumerate(range(0, m_, R)):
+        if chunks is not None and k >= chunks:
+            break
+        S1 += dy[r0:r0 + R].sum(0).double()
+        S2 += t2[r0:r0 + R].sum(0).double()
+    m1, m2, kk = (S1 / m_).float(), (S2 / m_).float(), gamma * st["invstd"]
+    return dict(s1=S1.float(), s2=S2.float(), dz=kk * ((dy - m1) - xhat * m2))
+
+
+def _worst(got, ref):
+    out = {}
+    for k, (r, bar) in ref.items():
+        ok, out[k] = H.inside(got[k], r, bar)
+        assert ok, (k, out[k])
+    return {k: round(v, 3) for k, v in out.items()}
+
+
+@pytest.mark.parametrize("m_", list(BIG))
+def test_f32_evaluations_pass_the_bars_past_16384_rows(m_):
+    assert (H.rows_per_chunk(m_), H.row_chunks(m_), m_ - (H.row_chunks(m_) - 1) * H.rows_per_chunk(m_), H.depth(m_)) == BIG[m_]
+    x = _big_rows(m_, 41)
+    gamma, beta, rm, rv = _stat_args()
+    ref = H.bn_stats(x.double(), gamma.double(), beta.double(), EPS, MOM, rm.double(), rv.double())
+    st = _stats32(x, gamma, beta, rm, rv)
+    print(f"M = {m_}: bn_stats, max err / bar", _worst(st, ref))
+    assert float(st["var"][1]) == 0.0 and float(st["mean"][1]) == 0.375
+    # the backward on the same rows: y = relu(fma) under the p = 0.5 mask
+    g = _rand((m_, 16), 42).float()
+    keep = synth.dropout_keep(m_, 16, 5, P)
+    y = torch.relu((x.double() * st["scale"].double() + st["shift"].double()).float()) * keep * 2
+    rb = H.bn_relu_backward(g.double(), y.double(), x.double(), st["mean"].double(), st["invstd"].double(), gamma.double(), 2.0, False)
+    print(f"M = {m_}: bn_relu_backward, max err / bar", _worst(_bwd32(g, y, x, st, gamma, 2.0), rb))
+
+
+@pytest.mark.parametrize("defect", ["tail_is_full", "first_batch_only", "reduce_in_32_rows"])
+def test_planted_size_defects_fail(defect):
+    m_ = 16420
+    x = _big_rows(m_, 41)
+    gamma, beta, rm, rv = _stat_args()
+    ref = H.bn_stats(x.double(), gamma.double(), beta.double(), EPS, MOM, rm.double(), rv.double())
+    got = _stats32(x, gamma, beta, rm, rv, defect=defect)
+    fails = {k: not H.inside(got[k], r, bar)[0] for k, (r, bar) in ref.items()}
+    ratio = {k: round(H.inside(got[k], r, bar)[1], 1) for k, (r, bar) in ref.items()}
+    print(defect, "max err / bar", ratio)
+    assert fails["mean"] and fails["var"] and fails["invstd"] and fails["shift"], (defect, ratio)      # a wrong count or a lost partial moves both moments
+    # ... on every column that has a spread; the constant column stays exact under a wrong count (every difference is 0)
+    r, bar = ref["mean"]
+    off = (got["mean"].double() - r).abs() > bar
+    assert bool(off[2:].all()) and bool(off[0]), (defect, off)
+
+
+def test_backward_sums_that_stop_after_the_first_batch_fail():
+    m_ = 16420
+    x = _big_rows(m_, 41)
+    gamma, beta, rm, rv = _stat_args()
+    st = _stats32(x, gamma, beta, rm, rv)
+    g = _rand((m_, 16), 42).float()
+    y = torch.relu((x.double() * st["scale"].double() + st["shift"].double()).float())
+    rb = H.bn_relu_backward(g.double(), y.double(), x.double(), st["mean"].double(), st["invstd"].double(), gamma.double(), 1.0, False)
+    got = _bwd32(g, y, x, st, gamma, 1.0, chunks=128)
+    assert not H.inside(got["s1"], *rb["s1"])[0] and not H.inside(got["s2"], *rb["s2"])[0] and not H.inside(got["dz"], *rb["dz"])[0]
+
+
+def test_keep_factor_that_is_no_power_of_two():
+    """p = 0.25: y = relu(fma(z, scale, shift)) * f32(4/3) in f32 — the fma's rounding, the factor's own and the product's: 3 u |y|, under the
+    2 x 2 u of H.bn_relu_drop.  A factor of 2 (p = 0.5's) or 1 (the mask without the scale) leaves it."""
+    m_, p = 1311, 0.25
+    z = _big_rows(m_, 43)
+    gamma, beta, rm, rv = _stat_args()
+    st = _stats32(z, gamma, beta, rm, rv)
+    keep = synth.dropout_keep(m_, 16, 7, p)
+    assert abs(float(keep.double().mean()) - 0.75) <= 4 * math.sqrt(0.1875 / keep.numel())
+    pre = torch.relu((z.double() * st["scale"].double() + st["shift"].double()).float())
+    factor = torch.tensor(1.0) / (torch.tensor(1.0) - torch.tensor(p))              # f32, as the launch function computes it
+    assert factor.dtype == torch.float32 and float(factor) != 4.0 / 3.0
+    ref, bar = H.bn_relu_drop(z.double(), st["scale"].double(), st["shift"].double(), keep, p, False)
+    ok, ratio = H.inside(pre * keep * factor, ref, bar)
+    print(f"p = 0.25 in f32: max err / bar {ratio:.3f}")
+    assert ok and bool((pre * keep * factor)[~keep].eq(0).all())
+    for wrong in (2.0, 1.0):
+        assert not H.inside(pre * keep * wrong, ref, bar)[0], wrong
+    assert not H.inside(pre * factor, ref, bar)[0]                                   # nothing dropped
 
 
 # ------------------------------------------------------------------------------------------------------------------ the dropout mask

@@ -2,7 +2,8 @@
 restatement (tests/seg_loss_f64.py) equals torch's own float64 F.interpolate + F.cross_entropy + autograd on every shape the GPU test runs;
 the same chain evaluated in float32 lies inside the derived f32 bars on every shape; and each constructed wrong variant — evaluated in
 float64, so that nothing but the defect separates it from the restatement — falls outside them.  A bar loosened later fails here before it
-reaches a kernel.  Also what needs no device: the entry points exist, refuse bad arguments before any device call, and refuse CPU tensors."""
+reaches a kernel.  The sweeps include the shape past 256 forward workgroups and the class counts 9, 16, 25, 32 of the GPU test; a loss whose
+sums stop after the first 256 partials is one of the wrong variants.  Also what needs no device: the entry points exist, refuse bad arguments before any device call, and refuse CPU tensors."""
 import ctypes as C
 
 import pytest
@@ -14,6 +15,9 @@ from wseg_amd import _lib as L
 
 HOST_SHAPES = S.SHAPES + [((2, 3), (11, 13), 2)]             # a batch of two with unequal valid counts: where a per-image count shows
 N_CLS = (21, 2)
+# the GPU sweep's cases (the shape past 256 partials at 21 classes only), the host's own batch of two, and the class counts of two and four chunks
+HOST_CASES = S.CLASS_CASES + [(HOST_SHAPES[-1], n) for n in N_CLS] + [(s, n) for s in S.NC8_SHAPES for n in S.NC8_COUNTS]
+HOST_SWEEP = [pytest.param(s, n, id=f"{S.shape_id(s)}-{n}") for s, n in HOST_CASES]
 
 
 def _torch_chain(coarse, label, dtype, align=True):
@@ -27,8 +31,7 @@ def _torch_chain(coarse, label, dtype, align=True):
     return dict(loss=loss.detach(), lse=torch.logsumexp(z.detach(), 1), grad=x.grad)
 
 
-@pytest.mark.parametrize("n_cls", N_CLS)
-@pytest.mark.parametrize("shape", HOST_SHAPES, ids=S.shape_id)
+@pytest.mark.parametrize("shape,n_cls", HOST_SWEEP)
 def test_restatement_equals_torch_float64(shape, n_cls):
     coarse, label = S.make_case(shape, n_cls, torch.float32, 11)
     ref, t = S.restate(coarse, label), _torch_chain(coarse, label, torch.float64)
@@ -46,8 +49,7 @@ def test_all_ignored_batch_is_torchs_answer(n_cls):
     assert S.within(t["grad"], ref["grad"], 0.0) and int(ref["count"]) == 0
 
 
-@pytest.mark.parametrize("n_cls", N_CLS)
-@pytest.mark.parametrize("shape", HOST_SHAPES, ids=S.shape_id)
+@pytest.mark.parametrize("shape,n_cls", HOST_SWEEP)
 def test_float32_chain_passes_the_bars(shape, n_cls):
     for dtype in (torch.float32, torch.bfloat16):                 # bf16: the VALUES are bf16-representable, the arithmetic stays f32
         coarse, label = S.make_case(shape, n_cls, dtype, 13)
@@ -104,6 +106,29 @@ def _applies(name, shape):
     if name == "count_per_image":
         return N > 1
     return True
+
+
+def test_a_loss_that_stops_after_256_partials_fails_the_bar():
+    """the finish kernel adds partial t, then t + 256: a loss whose sums end with the first 256 partials — the first 65536 label pixels — is what
+    a dropped second trip gives.  Evaluated in float64: nothing but the defect separates it from the restatement."""
+    shape = S.PAST_256_PARTIALS
+    assert S.forward_workgroups(shape) > 256
+    coarse, label = S.make_case(shape, 21, torch.float32, 14)
+    ref = S.restate(coarse, label)
+    z = torch.einsum("yi,ncij,xj->ncyx", ref["Wy"], coarse.double(), ref["Wx"])
+    lab = label.long()
+    nll = (torch.logsumexp(z, 1) - z.gather(1, lab.clamp(max=20)[:, None])[:, 0]).reshape(-1)
+    valid = ref["valid"].reshape(-1)
+    whole = torch.where(valid, nll, torch.zeros_like(nll))
+    assert S.within(whole.sum() / valid.sum(), ref["loss"], S.loss_bar(ref, coarse))                       # nothing planted: the restatement
+    assert bool(valid[65536:].any())
+    cut = whole[:65536].sum()
+    for name, loss in (("sum and count cut", cut / valid[:65536].sum()), ("sum cut", cut / valid.sum())):
+        err = abs(float(loss - ref["loss"]))
+        print(f"{name}: |loss - ref| {err:.3e}, bar {S.loss_bar(ref, coarse):.3e}")
+        assert not S.within(loss, ref["loss"], S.loss_bar(ref, coarse)), name
+    assert not S.within(cut, ref["nll_sum"], S.nll_sum_bar(ref, coarse))
+    assert float(valid[:65536].sum()) != float(ref["count"])                                              # (the counts are asserted as equalities)
 
 
 VARIANTS = ["align_corners_false", "mean_over_all_pixels", "ignored_pixels_get_gradient", "i1_dropped_at_the_end", "bf16_logits", "count_per_image"]
