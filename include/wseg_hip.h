@@ -366,6 +366,47 @@ typedef struct {
 size_t wseg_sizeof_aff_label_desc(void);
 int wseg_aff_labels_batch(const wseg_aff_label_desc* descs_dev, int n, int crop /* % 8 == 0 */, unsigned char* out_u8, void* stream);
 
+/* ---- DeepLab-v1 training data on the device (segmentation/lib/datasets/BaseDataset.py:88-98 __weak_augment__ with the transforms of
+ * lib/datasets/transform.py): RandomHSV on the decoded uint8 image -> RandomFlip (image and label, before the rescale) -> RandomScale (image
+ * cubic, label nearest) -> ImageNorm (float32 arithmetic: the table of wseg_aff_augment_batch) -> RandomCrop into a container of +0.0 (image)
+ * and 255 (label) -> CHW f32 image / uint8 label map.
+ *
+ * Two descriptor arrays sit side by side, one entry per image: wseg_aug_desc (layout unchanged; the resize passes read it as they do for
+ * wseg_augment_batch) and wseg_seg_data_desc.  Launches (blockIdx.y = image), selected by `stages`:
+ *   1  hsv      raw -> aug.src, pixelwise and out of place: 8-bit RGB -> HSV (H in [0, 180), integer arithmetic with the two division
+ *               tables), h = (h + dh) mod 180 (non-negative), s / v offset and clipped, HSV -> RGB in float32 (every product and difference
+ *               rounded on its own), written to column W-1-x where aug.flip is set: the resampler then reads a flipped source
+ *   2  resize   the two passes of Pillow's 8-bit bicubic resampler: aug.src -> aug.tmp -> aug.img (rh x rw)
+ *   4  finish   ONE launch writes both outputs: aug.out[3][crop][crop] = lut[c][img pixel] inside the pasted rectangle and +0.0 outside;
+ *               lab_out[y][x] = lab[yi[img_top + y - cont_top]][xi[img_left + x - cont_left]] inside and 255 outside.  yi [rh] / xi [rw]
+ *               are the host's nearest-neighbour source indices (float64 on the host; xi already composed with the flip), clamped to the
+ *               label on the device.  aug.flip is NOT applied here: the hsv launch did it.
+ * The hue shift, the colour ops and hue_shift of wseg_aug_desc are not read.  No atomics, no float64 on the device: the outputs are
+ * bit-identical from run to run.  The entry point reads the HOST copies of the descriptors and refuses, before any launch, n <= 0,
+ * crop <= 0, a null pointer a requested stage follows, non-positive sizes, ch / cw outside [1, crop] and a paste rectangle that leaves the
+ * container or the rescaled image; also raw / src off a 4-byte boundary and, at crop % 4 == 0 (rows of 16-byte stores), out off a 16-byte or
+ * lab_out off a 4-byte boundary.  Any other crop takes the scalar finish kernel. */
+typedef struct {
+  const uint8_t* raw;                                 /* decoded image [H][W][3] (H, W of the wseg_aug_desc beside it) */
+  const uint8_t* lab;                                 /* label map [H][W], unflipped */
+  const int32_t* yi; const int32_t* xi;               /* [rh], [rw] */
+  uint8_t* lab_out;                                   /* [crop][crop] */
+  int32_t dh, ds, dv;                                 /* RandomHSV offsets */
+  int32_t reserved;
+} wseg_seg_data_desc;
+size_t wseg_sizeof_seg_data_desc(void);
+#define WSEG_SEG_DATA_HSV 1
+#define WSEG_SEG_DATA_RESIZE 2
+#define WSEG_SEG_DATA_FINISH 4
+int wseg_seg_data_batch(const wseg_aug_desc* aug_host, const wseg_seg_data_desc* seg_host, const wseg_aug_desc* aug_dev,
+                        const wseg_seg_data_desc* seg_dev, int n, int crop, const float* lut /* [3][256], device */,
+                        const int32_t* hsv_div /* sdiv[256] then hdiv[256], device */, int stages, void* stream);
+/* launch geometry of wseg_seg_data_batch: out4 = { workgroups (of 256 threads) per image of the hsv launch for a largest image of
+ * max_pixels = H*W (4 pixels per thread), of each resize pass for max_pixels = max(H*rw, rh*rw) (1 per thread), of the finish launch, container
+ * pixels per finish thread (4, or 1 when crop % 4 != 0) }.  The hsv and resize launches walk their images in grid-stride loops (at most 1024
+ * workgroups per image); the finish launch has one thread per 4 (or 1) container pixels and no loop. */
+int wseg_seg_data_geometry(int max_pixels, int crop, int* out4);
+
 /* ---- fused SGD step (tool/torchutils.py:23-33 -> torch.optim.SGD.step) ------------------------
  * One pass over the flat buffers: d = g*grad_scale + wd*p; buf = first ? d : momentum*buf + d;
  * p -= lr*buf.  Segments [begin,end) carry the per-group lr / weight_decay (contrast_train.py:91-96).

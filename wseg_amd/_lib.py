@@ -520,6 +520,25 @@ def aff_labels_batch(descs_dev, n, crop, out_u8):
     _call("wseg_aff_labels_batch", _v(descs_dev), n, crop, _v(out_u8))
 
 
+# ---------------------------------------------------------------------------------------------- DeepLab-v1 training data (csrc/seg_data.hip)
+class SegDataDesc(C.Structure):                  # wseg_seg_data_desc
+    _fields_ = [("raw", C.c_void_p), ("lab", C.c_void_p), ("yi", C.c_void_p), ("xi", C.c_void_p), ("lab_out", C.c_void_p),
+                ("dh", C.c_int32), ("ds", C.c_int32), ("dv", C.c_int32), ("reserved", C.c_int32)]
+
+
+lib.wseg_sizeof_seg_data_desc.restype = C.c_size_t
+if lib.wseg_sizeof_seg_data_desc() != C.sizeof(SegDataDesc):
+    raise ImportError(f"wseg_seg_data_desc: library {lib.wseg_sizeof_seg_data_desc()} bytes, binding {C.sizeof(SegDataDesc)}: rebuild libwseg_hip.so")
+
+
+def seg_data_batch(aug_host, seg_host, aug_dev, seg_dev, n, crop, lut, hsv_div, stages=7):
+    """aug_host / seg_host: ctypes arrays of n wseg_aug_desc / wseg_seg_data_desc (the entry point checks them before any launch and raises
+    on a bad one); aug_dev / seg_dev: the addresses of their copies on the device; lut: f32 [3][256]; hsv_div: int32 sdiv[256], hdiv[256];
+    stages: 1 hsv | 2 resize | 4 finish."""
+    host = [C.c_void_p(C.addressof(a)) if a is not None else C.c_void_p(None) for a in (aug_host, seg_host)]
+    _call("wseg_seg_data_batch", *host, _v(aug_dev), _v(seg_dev), n, crop, _v(lut), _v(hsv_div), stages)
+
+
 # ---------------------------------------------------------------------------------------------- AffinityNet head, training (csrc/aff_head.hip)
 def elu_backward_rows(g, ld_g, y, ld_y, gscale, dz, ld_dz, M, C_):
     """dz[m, c] = gscale * g[m, c] * (y[m, c] > 0 ? 1 : y[m, c] + 1) for c < C_ on M pixel rows; y: the saved ELU output; gscale: a one-element

@@ -250,3 +250,194 @@ class VOC12AffDataset(VOC12ImageDataset):                  # voc12/data.py:201-2
         la = np.load(os.path.join(self.label_la_dir, name + '.npy'))
         ha = np.load(os.path.join(self.label_ha_dir, name + '.npy'))
         return aff_apply_transforms(img, la, ha, self.transforms)
+
+
+# ---------------------------------------------------------------------------------------------- DeepLab-v1 training data
+# The chain of segmentation/lib/datasets/BaseDataset.py:88-98 (__weak_augment__) with the transforms of lib/datasets/transform.py under
+# experiment/SEAM_deeplabv1_resnet38/config.py (crop 448, scale [0.5, 1.5], H/S/V 10/10/10, flip 0.5), on (image uint8 [H, W, 3], label
+# uint8 [H, W]) pairs.  The reference's RandomHSV and RandomScale call cv2, which is not available here: the 8-bit HSV arithmetic below is
+# OpenCV's definition restated, and Pillow's bicubic stands in for cv2.INTER_CUBIC (as in seg_infer) — both UNPINNED against cv2 itself
+# (DESIGN.md §8 9(c)).  RandomFlip, ImageNorm and the crop are pinned to the reference (tests/golden/seg_data_*.npz).  This is the host
+# path of DeepLab training data and what the device path (wseg_amd/seg_data.py) is held to, bit for bit.
+SEG_MEAN, SEG_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+HSV_SECTORS = ((1, 3, 0), (1, 0, 2), (3, 0, 1), (0, 2, 1), (0, 1, 3), (2, 1, 0))      # (b, g, r) in [V, p, q, t] per hue sector
+
+
+def hsv_div_tables():
+    """(sdiv, hdiv) int32 [256]: sdiv[i] = round(255 * 4096 / i), hdiv[i] = round(180 * 4096 / (6 * i)), both 0 at i = 0 (no quotient is
+    at a half: 255 * 2^12 and 15 * 2^13 have no factor 2 left for an i <= 255)"""
+    sdiv, hdiv = np.zeros(256, np.int32), np.zeros(256, np.int32)
+    for i in range(1, 256):
+        sdiv[i] = int(round(255 * 4096 / i))
+        hdiv[i] = int(round(180 * 4096 / (6 * i)))
+    return sdiv, hdiv
+
+
+def rgb2hsv_u8(rgb):
+    """uint8 [..., 3] RGB -> int32 (h in [0, 180), s, v in [0, 255]): the 8-bit conversion in integers, with the 12-bit division tables"""
+    sdiv, hdiv = hsv_div_tables()
+    c = np.asarray(rgb).astype(np.int32)
+    r, g, b = c[..., 0], c[..., 1], c[..., 2]
+    v = np.maximum(r, np.maximum(g, b))
+    diff = v - np.minimum(r, np.minimum(g, b))
+    s = (diff * sdiv[v] + 2048) >> 12
+    hn = np.where(v == r, g - b, np.where(v == g, b - r + 2 * diff, r - g + 4 * diff))      # ties: r, then g, then b
+    h = (hn * hdiv[diff] + 2048) >> 12                          # arithmetic shift
+    h = np.where(h < 0, h + 180, h)
+    return h, s, v
+
+
+def hsv2rgb_u8(h, s, v, sectors=HSV_SECTORS):
+    """integer h (degrees / 2), s, v in [0, 255] -> uint8 [..., 3] RGB in float32 arithmetic, every product and difference rounded on
+    its own, the result rounded half to even"""
+    f32 = np.float32
+    h, s, v = np.asarray(h), np.asarray(s), np.asarray(v)
+    S, V = s.astype(f32) / f32(255), v.astype(f32) / f32(255)
+    hh = h.astype(f32) * (f32(6) / f32(180))
+    while (hh < 0).any():
+        hh = np.where(hh < 0, hh + f32(6), hh)
+    while (hh >= 6).any():
+        hh = np.where(hh >= 6, hh - f32(6), hh)
+    fl = np.floor(hh)
+    sec, f = fl.astype(np.int32), hh - fl
+    bad = (sec < 0) | (sec >= 6)
+    sec, f = np.where(bad, 0, sec), np.where(bad, f32(0), f)
+    one = f32(1)
+    tab = np.stack([V, V * (one - S), V * (one - S * f), V * (one - S * (one - f))], axis=-1)
+    assert tab.dtype == np.float32
+    idx = np.asarray(sectors, np.int64)[sec]                    # [..., 3] = the table slots of (b, g, r)
+    bgr = np.take_along_axis(tab, idx, axis=-1)
+    bgr = np.where((s == 0)[..., None], V[..., None], bgr)
+    out = np.clip(np.rint(bgr * f32(255)), 0, 255).astype(np.uint8)
+    return out[..., ::-1]
+
+
+def hsv_jitter(img_u8, dh, ds, dv):
+    """transform.py:83-101 on a decoded uint8 RGB image with given offsets"""
+    h, s, v = rgb2hsv_u8(img_u8)
+    h = (h + dh) % 180                                          # Python's (numpy's) non-negative modulo
+    s = np.clip(s + ds, 0, 255)
+    v = np.clip(v + dv, 0, 255)
+    return np.ascontiguousarray(hsv2rgb_u8(h, s, v))
+
+
+def seg_scaled_size(h, w, scale):
+    """size after RandomScale: (round(H * s), round(W * s)), half to even as Python's round"""
+    rh, rw = int(round(h * scale)), int(round(w * scale))
+    if rh < 1 or rw < 1:
+        raise ValueError(f"RandomScale: {h} x {w} at scale {scale} leaves no pixel")
+    return rh, rw
+
+
+def nearest_index_table(n_in, n_out, scale):
+    """int32 [n_out]: the source index of every output position of a nearest-neighbour rescale by `scale`: min(floor(o * (1 / scale)),
+    n_in - 1) in float64, the reciprocal computed once"""
+    inv = 1.0 / float(scale)
+    return np.minimum(np.floor(np.arange(n_out, dtype=np.float64) * inv).astype(np.int64), n_in - 1).astype(np.int32)
+
+
+class RandomHSV:                                           # lib/datasets/transform.py:76-102
+    def __init__(self, h_r, s_r, v_r, rng=random):
+        self.h_r, self.s_r, self.v_r, self.rng = h_r, s_r, v_r, rng
+
+    def __call__(self, image, label):
+        dh = self.rng.randint(-self.h_r, self.h_r)
+        ds = self.rng.randint(-self.s_r, self.s_r)
+        dv = self.rng.randint(-self.v_r, self.v_r)
+        return hsv_jitter(image, dh, ds, dv), label
+
+
+class RandomFlip:                                          # lib/datasets/transform.py:104-124: np.flip(axis=1) of the image and the label
+    def __init__(self, threshold, rng=random):
+        self.flip_t, self.rng = threshold, rng
+
+    def __call__(self, image, label):
+        if self.rng.random() < self.flip_t:
+            image, label = np.flip(image, axis=1), np.flip(label, axis=1)
+        return image, label
+
+
+class RandomScale:                                         # lib/datasets/transform.py:126-149: the image cubic, the label nearest
+    def __init__(self, scale_r, rng=random):
+        self.scale_r, self.rng = scale_r, rng
+
+    def __call__(self, image, label):
+        h, w = image.shape[:2]
+        scale = self.rng.random() * (self.scale_r[1] - self.scale_r[0]) + self.scale_r[0]
+        rh, rw = seg_scaled_size(h, w, scale)
+        image = np.asarray(PIL.Image.fromarray(np.ascontiguousarray(image)).resize((rw, rh), BICUBIC))
+        label = label[nearest_index_table(h, rh, scale)][:, nearest_index_table(w, rw, scale)]
+        return image, label
+
+
+class ImageNorm:                                           # lib/datasets/transform.py:151-168: float32 arithmetic on the float32 image
+    def __init__(self, mean=SEG_MEAN, std=SEG_STD):
+        self.mean, self.std = mean, std
+
+    def __call__(self, image, label):
+        image = image.astype(np.float32)
+        for c in range(3):
+            image[..., c] = (image[..., c] / 255 - self.mean[c]) / self.std[c]
+        return image, label
+
+
+class SegRandomCrop:
+    """lib/datasets/transform.py:12-74: the width draw before the height draw; the float32 image into a ZERO container (the padding is
+    +0.0, not normalize(0)), the label into a container of 255."""
+
+    def __init__(self, output_size, rng=random):
+        self.output_size, self.rng = (output_size, output_size) if isinstance(output_size, int) else tuple(output_size), rng
+
+    def __call__(self, image, label):
+        h, w = image.shape[:2]
+        oh, ow = self.output_size
+        ch, cw = min(h, oh), min(w, ow)
+        h_space, w_space = h - oh, w - ow
+        if w_space > 0:
+            cont_left, img_left = 0, self.rng.randrange(w_space + 1)
+        else:
+            cont_left, img_left = self.rng.randrange(-w_space + 1), 0
+        if h_space > 0:
+            cont_top, img_top = 0, self.rng.randrange(h_space + 1)
+        else:
+            cont_top, img_top = self.rng.randrange(-h_space + 1), 0
+        img_crop = np.zeros((oh, ow, 3), np.float32)
+        img_crop[cont_top:cont_top + ch, cont_left:cont_left + cw] = image[img_top:img_top + ch, img_left:img_left + cw]
+        seg_crop = np.full((oh, ow), 255, label.dtype)
+        seg_crop[cont_top:cont_top + ch, cont_left:cont_left + cw] = label[img_top:img_top + ch, img_left:img_left + cw]
+        return img_crop, seg_crop
+
+
+def seg_train_transform(crop=448, scale_r=(0.5, 1.5), hsv_r=(10, 10, 10), flip_p=0.5, rng=random):
+    """BaseDataset.py:88-98 under config.py: RandomHSV -> RandomFlip -> RandomScale -> ImageNorm -> RandomCrop"""
+    return [RandomHSV(*hsv_r, rng=rng), RandomFlip(flip_p, rng=rng), RandomScale(scale_r, rng=rng), ImageNorm(), SegRandomCrop(crop, rng=rng)]
+
+
+def seg_apply_transforms(image, label, transforms):
+    """(img float32 [3, crop, crop], label uint8 [crop, crop]: 0..20 a class, 255 ignore) of one decoded sample (ToTensor's CHW; the
+    reference's int64 label is emitted as uint8, the form seg_loss.seg_cross_entropy accepts)"""
+    image, label = np.asarray(image, np.uint8), np.asarray(label, np.uint8)
+    if image.ndim != 3 or image.shape[2] != 3 or label.shape != image.shape[:2]:
+        raise ValueError(f"seg_apply_transforms: image {image.shape} with label {label.shape}")
+    for t in transforms:
+        image, label = t(image, label)
+    return np.ascontiguousarray(HWC_to_CHW(image)), np.ascontiguousarray(label)
+
+
+def load_seg_label(path):
+    """a label PNG (palette or greyscale: the stored indices) as uint8 [H, W] (VOCDataset.py load_pseudo_segmentation / load_segmentation)"""
+    return np.asarray(PIL.Image.open(path), dtype=np.uint8)
+
+
+class VOCSegTrainDataset(VOC12ImageDataset):
+    """(img float32 [3, crop, crop], label uint8 [crop, crop]) per image on the host: the CPU path of DeepLab-v1 training data and the
+    yardstick of the device path (wseg_amd/seg_data.py).  Labels: `<pseudo_gt_dir>/<name>.png`."""
+
+    def __init__(self, img_name_list_path, voc12_root, pseudo_gt_dir, transforms=None):
+        super().__init__(img_name_list_path, voc12_root, transform=None)
+        self.pseudo_gt_dir, self.transforms = pseudo_gt_dir, transforms or seg_train_transform()
+
+    def __getitem__(self, idx):
+        name, img = super().__getitem__(idx)
+        label = load_seg_label(os.path.join(self.pseudo_gt_dir, name + '.png'))
+        return seg_apply_transforms(np.asarray(img), label, self.transforms)

@@ -9,8 +9,10 @@ backbone runs through wseg_amd.engine (the contrast net's kernels and packs), th
 epilogue's shift), the resample to the input size in csrc/seg.hip.  Inference only: in training mode `forward` raises.  Of the training
 stage the loss layer exists — wseg_amd.seg_loss.seg_cross_entropy, the cross-entropy of the resampled coarse logits and its gradient on the
 cls_conv rows (csrc/seg_loss.hip) — and the head layer: wseg_amd.seg_head, the head's training forward (BatchNorm on batch statistics, dropout)
-and its backward down to t = relu(bn7(conv6)) (csrc/seg_head.hip).  The backbone's backward from there, the data path and the trainer do not
-exist yet, so `forward` keeps refusing training mode.
+and its backward down to t = relu(bn7(conv6)) (csrc/seg_head.hip) — and the data path: wseg_amd.seg_data.DeviceSegData turns decoded images
+and label PNGs into the (img float32 [N, 3, crop, crop], label uint8 [N, crop, crop]) pair of a training step on the device (csrc/seg_data.hip;
+host chain: wseg_amd.data.VOCSegTrainDataset).  The backbone's backward from t and the trainer do not exist yet, so `forward` keeps refusing
+training mode.
 """
 import os
 
