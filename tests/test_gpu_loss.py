@@ -660,7 +660,8 @@ def test_packs_follow_the_weights_bf16(proc_sd):
     P = eng.ensure_packs(torch.device("cuda", torch.cuda.current_device()), L.BF16)      # (+ the deferred transposed packs)
     torch.cuda.synchronize()
     changed = 0
-    for name in ("b7.conv_branch1", "b7.conv_branch2b2", "b7.conv_branch2a", "b6.conv_branch1", "b5.conv_branch2b1", "b5.conv_branch2a", "b4_2.conv_branch2a"):
+    for name in ("b7.conv_branch1", "b7.conv_branch2b2", "b7.conv_branch2a", "b6.conv_branch1", "b5.conv_branch2b1", "b5.conv_branch2a", "b5.conv_branch1",
+                 "b4_2.conv_branch2a"):
         w = eng.conv_param(name).detach()                                   # logical [OC, IC, KH, KW] view of the master
         okkc = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1, w.shape[1]).to(torch.bfloat16)
         assert torch.equal(P["w"][name], okkc), name
@@ -673,3 +674,8 @@ def test_packs_follow_the_weights_bf16(proc_sd):
         ft = P["wt"][blk + ".skip_fused"]
         assert torch.equal(ft.reshape(ft.shape[0], -1), torch.cat([P["wt"][f"{blk}.conv_branch1"].reshape(ft.shape[0], -1),
                                                                      P["wt"][f"{blk}.conv_branch2a"].reshape(ft.shape[0], -1)], dim=1))
+    # b5, the ResBlock form: forward [conv_branch2b1, nine taps | conv_branch1], transposed [conv_branch2a, nine taps | conv_branch1]
+    f, ft = P["w"]["b5.skip_fused"], P["wt"]["b5.skip_fused"]
+    assert f.shape == (1024, 9 * 512 + 512) and ft.shape == (512, 9 * 512 + 1024)
+    assert torch.equal(f, torch.cat([P["w"]["b5.conv_branch2b1"].reshape(1024, -1), P["w"]["b5.conv_branch1"].reshape(1024, -1)], dim=1))
+    assert torch.equal(ft, torch.cat([P["wt"]["b5.conv_branch2a"].reshape(512, -1), P["wt"]["b5.conv_branch1"].reshape(512, -1)], dim=1))
