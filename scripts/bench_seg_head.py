@@ -64,7 +64,7 @@ def main():
         eng.flat_g.zero_()
         cap = {}
         d_t = seg_head_backward(ctx, d_rows, capture=cap)
-        P = eng.seg_head_wt(t.device)
+        P = eng.head_wt(t.device)
 
         # the same chain in plain torch, in the mode's storage dtype
         x0 = t.view(N, h, w, 4096).permute(0, 3, 1, 2).contiguous().requires_grad_()

@@ -55,7 +55,7 @@ def test_affinity_head_refuses_the_cpu():
     # the transposed-pack table: the four masters close the flat buffers in the order f8_3, f8_4, f8_5, f9; packs are [IC][1][OC]
     eng = net._engine
     eng._ensure_flat(torch.device("cpu"))
-    specs = eng.aff_head_wt_specs()
+    specs = eng.head_wt_specs()
     assert [s[0] for s in specs] == ["f8_3", "f8_4", "f8_5", "f9"]
     assert [s[3] for s in specs] == [(512, 1, 64), (1024, 1, 128), (4096, 1, 256), (448, 1, 448)]
     end = eng.flat_w.numel()

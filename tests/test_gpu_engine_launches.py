@@ -1,9 +1,12 @@
-"""The launch sequence of the engine's four paths, pinned: every launching call of wseg_amd._lib in call order, with its scalars, its
+"""The launch sequence of the engine's paths, pinned: every launching call of wseg_amd._lib in call order, with its scalars, its
 tensor operands (dtype and element offset within the storage: a wrong column slice such as feat.view(-1)[64:] shows) and the role of
 the stream it is enqueued on, compared as a whole list against tests/golden/engine_launches_<case>.json.  A host-side refactor of
 engine.py must leave every one of them as it is: the fixtures are written once, at the commit BEFORE such a change,
-  python tests/test_gpu_engine_launches.py --write
-and are not regenerated after it (the committed ones: at ae4165a, before the trunk / heads split of the engine).  Shapes: the smallest that still take every branch of both block loops (same and non-same ResBlocks,
+  python tests/test_gpu_engine_launches.py --write [case ...]
+and are not regenerated after it.  The committed ones: contrast_step, net_autograd, aff_train, contrast_infer, aff_infer at ae4165a, before
+the trunk / heads split of the engine; seg_infer and seg_head_train (the DeepLab head, which those predate) at 4989fae, with this file's
+cases run on that commit's wseg_amd/, before the frozen prefix moved into the net classes and the head passes were shared.
+Shapes: the smallest that still take every branch of both block loops (same and non-same ResBlocks,
 fused and unfused skip, bottleneck blocks, taps on b5 and b6, two row segments of odd, unequal stride-8 maps 13x9 and 5x7)."""
 import inspect
 import json
@@ -171,9 +174,48 @@ def aff_infer(rec_of, prec):
     return rec
 
 
+def _seg_net(prec, train):
+    from wseg_amd import synth
+    from wseg_amd.deeplabv1_resnet38 import Net
+    m = Net(precision=prec)
+    m.load_state_dict(synth.procedural_seg_state_dict(0))
+    m.cuda()
+    return m.train() if train else m.eval()
+
+
+def seg_infer(rec_of, prec):
+    """(e) DeepLab Net.coarse_logits: the backbone and the eval head, one image"""
+    from wseg_amd import synth
+    m = _seg_net(prec, False)
+    x = synth.synthetic_images(1, 64, 29).cuda()
+    rec = rec_of(m._engine)
+    m.coarse_logits(x)
+    return rec
+
+
+def seg_head_train(rec_of, prec):
+    """(f) the DeepLab head's training forward and its backward with the bn7-ReLU operands, N = 2 on an 8 x 8 map"""
+    from wseg_amd import seg_head, synth
+    from wseg_amd.engine import DT_OF
+    from wseg_amd import _lib as L
+    N, h, w = 2, 8, 8
+    m = _seg_net(prec, True)
+    g = torch.Generator().manual_seed(31)
+    tdt = L.TORCH_DTYPE[DT_OF[prec]]
+    t = torch.relu(torch.randn(N * h * w, 4096, generator=g)).to(tdt).cuda()
+    d_rows = torch.zeros(N * h * w, 24)
+    d_rows[:, :21] = torch.rand(N * h * w, 21, generator=g) * 2 - 1
+    scale = (torch.rand(4096, generator=g) + 0.5).cuda()
+    rec = rec_of(m._engine)
+    _rows, ctx = seg_head.seg_head_forward(m, t, N, h, w, synth.dropout_key(3, h))
+    seg_head.seg_head_backward(ctx, d_rows.cuda(), scale=scale, mask=t)
+    return rec
+
+
 CASES = [("contrast_step", contrast_step, "bf16"), ("contrast_step", contrast_step, "bf16x3"), ("net_autograd", net_autograd, "fp32"),
          ("aff_train", aff_train, "bf16"), ("aff_train", aff_train, "fp32"), ("contrast_infer", contrast_infer, "bf16"),
-         ("aff_infer", aff_infer, "bf16")]
+         ("aff_infer", aff_infer, "bf16"), ("seg_infer", seg_infer, "bf16"), ("seg_head_train", seg_head_train, "fp32"),
+         ("seg_head_train", seg_head_train, "bf16")]
 
 
 def _path(name, prec):
@@ -197,8 +239,12 @@ def test_launch_sequence_is_the_pinned_one(monkeypatch, name, case, prec):
 
 
 if __name__ == "__main__":
-    assert sys.argv[1:] == ["--write"], "usage: python tests/test_gpu_engine_launches.py --write   (at the commit BEFORE an engine change)"
+    assert sys.argv[1:2] == ["--write"], "usage: python tests/test_gpu_engine_launches.py --write [case ...]   (at the commit BEFORE an engine change)"
+    only = sys.argv[2:]                                # new cases alone: the fixtures of the others stay as they were written
+    assert set(only) <= {n for n, _c, _p in CASES}, only
     for name, case, prec in CASES:
+        if only and name not in only:
+            continue
         with pytest.MonkeyPatch.context() as mp:
             calls = _run(case, prec, mp)
         with open(_path(name, prec), "w") as f:

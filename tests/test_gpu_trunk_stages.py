@@ -17,7 +17,7 @@ is printed): the engine's pair OPERANDS are judged here through the weight gradi
 
 Cost.  The GPU work of a case is milliseconds; the float64 references on the CPU are the cost.  Measured per mode on the 16 cores of an
 MI355X host (on 8 cores: 2.0 s and 4.7 s for the first two): contrast forward (100 x 76 + 44 x 28, N = 2, 308 stride-8 pixels) 1.2 - 1.3 s,
-contrast backward 4.3 - 4.6 s, AffinityNet backbone forward and backward (84 x 60, N = 2) 3.5 - 3.8 s, eval forward (84 x 60, N = 1) 0.2 s.
+contrast backward 4.3 - 4.6 s, AffinityNet backbone forward and backward (84 x 60, N = 2) 3.5 - 3.8 s (with b3 frozen too: 3.2 - 3.5 s), eval forward (84 x 60, N = 1) 0.2 s.
 The per-stage table of an MI355X run: profiles/r25_trunk_stages_f64.txt."""
 import time
 
@@ -45,6 +45,8 @@ def _net(kind, mode):
             m.load_state_dict(synth.procedural_state_dict(0), strict=True)
         else:
             from wseg_amd.resnet38_aff import Net
+            if kind == "aff_b3":                              # the AffinityNet with b3 frozen too: b3_1 is the first trainable block
+                Net = type("NetB3Frozen", (Net,), {"FROZEN_BLOCKS": arch.FROZEN_BLOCKS + ("b3",)})
             m = Net(precision=mode)
             m.load_state_dict(synth.procedural_aff_state_dict(0), strict=True)
         _NETS[(kind, mode)] = m.cuda()
@@ -57,7 +59,7 @@ def _trunk_conv_names():
 
 def _weights(kind, eng, mode):
     """the trunk's weights from the module's parameters, rounded as the mode stores them (fp32 and bf16x3 store the same f32 values)"""
-    key = (kind, "bf16" if mode == "bf16" else "f32")
+    key = (kind[:3], "bf16" if mode == "bf16" else "f32")             # ("aff" and "aff_b3" load the same state dict)
     if key not in _W:
         while len(_W) >= 2:                                   # (0.8 GB of float64 each)
             del _W[next(iter(_W))]
@@ -170,9 +172,11 @@ class Recorder:
         """adds D, tap, du | du2, du1, tmp, D_in and the weight gradients (read from the flat gradient buffer) to the trainable blocks' records;
         returns the splits {block: {stage: n}}"""
         eng, splits = self.eng, {}
+        frozen = eng.net.FROZEN_BLOCKS
+        first = arch.BLOCKS[len(frozen)][0]                   # the first trainable block: weight gradients only
         for b in reversed(arch.BLOCKS):
             name, kind = b[0], b[1]
-            if name in arch.FROZEN_BLOCKS:
+            if name in frozen:
                 assert not any(k.split(".")[0] == name for k in self.dgrads)
                 continue
             r = rec[name]
@@ -191,7 +195,7 @@ class Recorder:
             if "conv_branch1" in g:
                 r["tmp"] = g["conv_branch1"][1]
             last = g.get("skip_fused") or g.get("conv_branch2a")
-            if name == "b3":
+            if name == first:
                 assert last is None and "tmp" not in r
             else:
                 r["D_in"] = D = last[1]
@@ -260,7 +264,7 @@ def _run(kind, mode, monkeypatch, views, N, train, backward):
     xs = [synth.synthetic_images(N, hw, 7 + i).cuda() for i, hw in enumerate(views)]
     rec = Recorder(monkeypatch, eng)
     with torch.no_grad():
-        if kind == "aff":
+        if kind != "contrast":
             _st, _ps, S = eng.run_backbone(xs, save=True)
         else:
             _st, _ps, S = eng._run_trunk(xs, train, eng.MASK_SPECS if train else None, keep_frozen=train)
@@ -284,19 +288,19 @@ def _run(kind, mode, monkeypatch, views, N, train, backward):
             print(f"[{kind} {mode}] paired data gradient: fused {fused}, {dg}, weight gradient {wg}")
         assert (len(rec.pairs) > 0) == (mode == "bf16")
         for n in _trunk_conv_names():                           # the frozen prefix gets no gradient, nor does any BatchNorm
-            frozen = n == "conv1a" or n.split(".")[0] in arch.FROZEN_BLOCKS
+            frozen = n == "conv1a" or n.split(".")[0] in net.FROZEN_BLOCKS
             assert (n in eng.offsets) != frozen and (eng.conv_param(n).grad is None) == frozen, n
         for n in T.bn_names():
             bnm = eng.bn_module(n)
             assert bnm.weight.grad is None and bnm.bias.grad is None, n
     torch.cuda.synchronize()
-    return _cpu(record), W, bn, masks, splits
+    return _cpu(record), W, bn, masks, splits, net.FROZEN_BLOCKS
 
 
 def _judge(tag, mode, data, N, forward, backward):
-    record, W, bn, masks, splits = data
+    record, W, bn, masks, splits, frozen = data
     t0 = time.perf_counter()
-    table = T.judge(mode, record, W, bn, masks, N, splits=splits, forward=forward, backward=backward)
+    table = T.judge(mode, record, W, bn, masks, N, splits=splits, forward=forward, backward=backward, frozen=frozen)
     _report(tag, mode, table, time.perf_counter() - t0)
     return table
 
@@ -331,6 +335,20 @@ def test_aff_backbone(monkeypatch, mode):
     data = _run("aff", mode, monkeypatch, (ONE_VIEW,), 2, True, True)
     table = _judge("aff backbone", mode, data, 2, True, True)
     assert sum(".dW_" in row[0] for row in table) == 35
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_aff_backbone_longer_prefix(monkeypatch, mode):
+    """the same pass with another prefix, read from the net: b3 frozen too.  b3_1, a same-shape block, is then the first trainable one: weight
+    gradients only (its 256 -> 256 3x3 conv_branch2a's on its own launch), no D_in, and nothing of b3 runs backward or has a gradient slot
+    (_run asserts the offsets and the .grad of every conv against the net's FROZEN_BLOCKS)."""
+    data = _run("aff_b3", mode, monkeypatch, (ONE_VIEW,), 2, True, True)
+    assert data[5] == ("b2", "b2_1", "b2_2", "b3")
+    table = _judge("aff backbone, b3 frozen", mode, data, 2, True, True)
+    tags = {row[0] for row in table}
+    assert sum(".dW_" in t_ for t_ in tags) == 32              # 35 less b3's three
+    assert {"b3_1.du", "b3_1.dW_2a", "b3_1.dW_2b1", "b3_2.D_in"} <= tags and "b3_1.D_in" not in tags
+    assert not any(t_.split(".")[0] == "b3" and t_.split(".")[1] in T.BWD_STAGES for t_ in tags)
 
 
 @pytest.mark.parametrize("mode", MODES)

@@ -169,6 +169,59 @@ def test_gradient_buckets_tile_the_flat_buffer():
                 assert blk in done or blk in ("fc_proj", "fc8", "f8_3", "f8_4", "f9"), (trigger, name)
 
 
+def _aff_net_frozen(frozen):
+    from wseg_amd.resnet38_aff import Net
+    return type("NetWithPrefix", (Net,), {"FROZEN_BLOCKS": tuple(frozen)})(precision="fp32")
+
+
+@pytest.mark.parametrize("extra", [None, 1, 3, 4], ids=["none", "b2", "shipped", "shipped+b3"])
+def test_frozen_prefix_host_arithmetic(extra):
+    """Everything the engine derives from the net's FROZEN_BLOCKS, for four prefixes: the flat-buffer order and size, the gradient buckets,
+    the shape of the prefix's output, and what train() freezes."""
+    from wseg_amd import arch
+    names = [b[0] for b in arch.BLOCKS]
+    frozen = () if extra is None else tuple(names[:extra])
+    assert arch.FROZEN_BLOCKS == tuple(names[:3]) and (extra != 4 or frozen == arch.FROZEN_BLOCKS + ("b3",))
+    net = _aff_net_frozen(frozen)
+    eng = net._engine
+    eng.ensure_flat(torch.device("cpu"))
+    trainable = [b for b in arch.BLOCKS if b[0] not in frozen]
+    want = [c[0] for b in trainable for c in arch.block_convs(b)] + ["f8_3", "f8_4", "f8_5", "f9"]
+    assert eng.trainable_order() == want
+    total = sum(eng.conv_param(n).numel() for n in want)
+    assert eng.flat_w.numel() == total == eng.flat_g.numel()
+    off = 0
+    for n in want:                                             # the offsets tile the buffer in that order
+        assert eng.offsets[n] == (off, eng.conv_param(n).numel()), n
+        off += eng.offsets[n][1]
+    assert off == total and set(eng.offsets) == set(want)
+    buckets = eng.grad_buckets()
+    spans = sorted(buckets.values())
+    assert spans[0][0] == 0 and spans[-1][1] == eng.flat_g.numel() and all(a[1] == b[0] for a, b in zip(spans, spans[1:]))
+    assert list(buckets)[-1] == trainable[0][0] and buckets[trainable[0][0]][0] == 0
+    N, dims = 2, [(84, 60)]
+    for b in arch.BLOCKS:
+        if b[0] in frozen:
+            dims = arch.block_out_dims(b, dims)
+    channels = arch.BLOCKS[len(frozen) - 1][4] if frozen else 64
+    assert eng.prefix_out_shape([torch.zeros(N, 3, 84, 60)]) == (N * dims[0][0] * dims[0][1], channels)
+    net.train()
+    assert not net.conv1a.weight.requires_grad
+    for b in arch.BLOCKS:
+        for c in arch.block_convs(b):
+            assert eng.conv_param(c[0]).requires_grad == (b[0] not in frozen), c[0]
+    assert all(getattr(net, n).weight.requires_grad for n in ("f8_3", "f8_4", "f8_5", "f9"))
+
+
+@pytest.mark.parametrize("frozen", [("b2_1",), ("b2", "b2_1", "b2_2", "b3", "b3_1", "b3_2", "b4", "b4_1", "b4_2", "b4_3", "b4_4", "b4_5", "b5", "b5_1",
+                                                "b5_2")], ids=["not-leading", "bottleneck-first"])
+def test_engine_refuses_a_prefix_it_cannot_serve(frozen):
+    """a prefix that is no leading run of the blocks, and one that leaves a bottleneck as the first trainable block: refused, naming the net"""
+    net = _aff_net_frozen(frozen)
+    with pytest.raises(ValueError, match="NetWithPrefix"):
+        net._engine.ensure_flat(torch.device("cpu"))
+
+
 def test_block_launch_convs_restate_nothing():
     """engine.block_launch_convs is arch.block_convs with dims: the same (name, cin, cout, k, stride, dilation) set for every block, and
     launch geometry (IH, IW / OH, OW / pad / the second view's row segment) equal to what block_out_dims gives, worked out here on

@@ -382,9 +382,10 @@ def block_backward(A, name, r, W, bn, masks, N, din, fused=False, splits=None, f
 
 
 # ------------------------------------------------------------------------------------------------------------------ chain and judge
-def run_chain(A, xs, W, bn, masks, fused=(), D=None, taps=None):
+def run_chain(A, xs, W, bn, masks, fused=(), D=None, taps=None, frozen=FROZEN):
     """The whole trunk on its own outputs under arithmetic A (Emu or Exact): the record {"stem": {..}, block: {every stored tensor}} a judge
-    reads; with D (the gradient at b7's x_out, rows) the backward down to b3 too, taps {block: gradient w.r.t. that block's t}."""
+    reads; with D (the gradient at b7's x_out, rows) the backward down to the first block behind `frozen` (a leading run of ORDER) too, taps
+    {block: gradient w.r.t. that block's t}."""
     N, dims = xs[0].shape[0], [tuple(x.shape[2:]) for x in xs]
     rec = {"stem": dict(stem_forward(A, xs, W, bn), dims=dims, x=xs)}
     t, x = rec["stem"]["t_out"], None
@@ -398,13 +399,13 @@ def run_chain(A, xs, W, bn, masks, fused=(), D=None, taps=None):
     if D is None:
         return rec
     for name in reversed(ORDER):
-        if name in FROZEN:
+        if name in frozen:
             break
         r = rec[name]
         r["D"] = D
         if taps and name in taps:
             r["tap"] = taps[name]
-        first = ORDER[ORDER.index(name) - 1] in FROZEN
+        first = name == ORDER[len(frozen)]
         r.update(block_backward(A, name, r, W, bn, masks, N, r["dims"], fused=name in fused, first=first))
         D = r.get("D_in")
     return rec
@@ -427,10 +428,10 @@ def judge_stage(tag, got, ref, bar, table):
     return ok
 
 
-def judge(mode, rec, W, bn, masks, N, splits=None, backward=True, forward=True, table=None):
+def judge(mode, rec, W, bn, masks, N, splits=None, backward=True, forward=True, table=None, frozen=FROZEN):
     """Every stored tensor of the record against its stage's float64 reference computed from the record's own stored inputs.
     A block's structure is read off its record: `rpost` / `tmp` present = the skip conv's output was stored first; absent (and a skip conv
-    exists) = one K-concatenated launch.  Returns the table [(tag, max err, max err / bar, ok)]."""
+    exists) = one K-concatenated launch.  frozen: the net's frozen blocks, the block behind them gets weight gradients only.  Returns the table [(tag, max err, max err / bar, ok)]."""
     A, table = Ref(mode), [] if table is None else table
     if forward and "x" in rec.get("stem", {}):
         ref = stem_forward(A, rec["stem"]["x"], W, bn)
@@ -449,7 +450,7 @@ def judge(mode, rec, W, bn, masks, N, splits=None, backward=True, forward=True, 
                     else:
                         assert st == "x_out", (name, st)           # the one output an implementation may keep to itself
         if backward and "D" in r:
-            first = ORDER[ORDER.index(name) - 1] in FROZEN
+            first = name == ORDER[len(frozen)]
             ref = block_backward(A, name, r, W, bn, masks, N, r["dims"], fused=skip and "tmp" not in r, splits=(splits or {}).get(name),
                                  first=first)
             for st in BWD_STAGES:

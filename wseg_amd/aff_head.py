@@ -20,23 +20,20 @@ The f8_5 data gradient takes the optional BN-ReLU backward operands of the contr
 Every data gradient and its weight gradient are two launches (the joint grid of wseg_conv_bwd_pair is not used here).  Nothing
 synchronises with the host.  The rest of the step — the backbone's backward with gradient taps, trainer, CLI — is wseg_amd/aff_train.py.
 """
+import functools
+
 import torch
 
 from . import arch
 from . import _lib as L
-from .engine import AFF_FEAT_C, AFF_FEAT_SLICES, DT_OF, Conv
+from .engine import AFF_FEAT_C, AFF_FEAT_SLICES, DT_OF, device_only, grad_to_rows, head_backward_launchers, head_conv, nchw_to_rows, rows_to_nchw
 
 BRANCHES = (("f8_3", "conv4"), ("f8_4", "conv5"), ("f8_5", "t"))     # (conv, the name of its input in the context)
-
-
-def _device_only(t, what):
-    if not t.is_cuda:
-        raise RuntimeError(f"wseg_amd.aff_head runs only on an MI355X (HIP) device; there is no CPU fallback ({what} is on {t.device})")
-
+_device_only = functools.partial(device_only, "aff_head")
 
 def _conv(name, dims):
     cout, cin = arch.AFF_HEAD_CONVS[name]
-    return Conv(name, cin, cout, 1, 1, 1, dims, dims)
+    return head_conv(name, cin, cout, dims)
 
 
 def backward_launches(N, h, w, dt, epi1=False):
@@ -85,22 +82,13 @@ def aff_head_backward(ctx, d_f9, gscale=None, scale=None, mask=None, drop=None, 
         _device_only(gscale, "gscale")
         gscale = gscale.reshape(-1)[:1].float().contiguous()
     dev = d_f9.device
-    P = eng.aff_head_wt(dev)
+    P = eng.head_wt(dev)
     eng.attach_grads()
     launches = backward_launches(N, h, w, dt, epi1=any(o is not None for o in (scale, mask, drop)))
+    wgrad, dgrad = head_backward_launchers(eng, P, launches, capture)
 
     def E(c):
         return torch.empty(M, c, device=dev, dtype=tdt)
-
-    def wgrad(name, x, dy):
-        if eng.conv_param(name).requires_grad:
-            L.conv_wgrad(x, dy, eng.grad_slice(name), **launches["wgrad_" + name])
-
-    def dgrad(name, dy, out, **operands):
-        kw = dict(launches["dgrad_" + name], **operands)
-        if capture is not None:
-            capture.setdefault("plans", {})[name] = L.conv_plan(dy, P["wt"][name], out, None, **kw)
-        L.conv_igemm(dy, P["wt"][name], out, None, **kw)
 
     dz9 = E(C)
     L.elu_backward_rows(d_f9, d_f9.stride(0), ctx["f9"], C, gscale, dz9, C, M, C)
@@ -124,21 +112,6 @@ def aff_head_backward(ctx, d_f9, gscale=None, scale=None, mask=None, drop=None, 
     return tuple(outs)
 
 
-def _rows(x, tdt):
-    """NCHW -> contiguous pixel rows [N*h*w, C] in tdt (a channels_last tensor of that dtype is taken as it is)"""
-    N, C, h, w = x.shape
-    r = x.detach().permute(0, 2, 3, 1)
-    if r.dtype != tdt:
-        r = r.to(tdt)
-    return r.contiguous().view(N * h * w, C)
-
-
-def _nchw(rows, N, h, w, dtype):
-    """pixel rows -> the NCHW view in channels_last strides, in `dtype`"""
-    v = rows.view(N, h, w, rows.shape[1]).permute(0, 3, 1, 2)
-    return v if v.dtype == dtype else v.to(dtype)
-
-
 class AffinityHead(torch.autograd.Function):
     """f9 = AffinityHead.apply(conv4, conv5, conv6, anchor, net): see affinity_head."""
 
@@ -146,10 +119,10 @@ class AffinityHead(torch.autograd.Function):
     def forward(ctx, conv4, conv5, conv6, anchor, net):
         N, _, h, w = conv6.shape
         tdt = L.TORCH_DTYPE[DT_OF[net.precision]]
-        f9, ctx.saved = aff_head_forward(net, _rows(conv4, tdt), _rows(conv5, tdt), _rows(conv6, tdt), N, h, w)
+        f9, ctx.saved = aff_head_forward(net, nchw_to_rows(conv4, tdt), nchw_to_rows(conv5, tdt), nchw_to_rows(conv6, tdt), N, h, w)
         ctx.in_dtypes = (conv4.dtype, conv5.dtype, conv6.dtype)
         ctx.set_materialize_grads(False)
-        return _nchw(f9, N, h, w, f9.dtype)
+        return rows_to_nchw(f9, N, h, w, f9.dtype)
 
     @staticmethod
     def backward(ctx, g):
@@ -157,14 +130,8 @@ class AffinityHead(torch.autograd.Function):
             return None, None, None, None, None
         s = ctx.saved
         N, h, w = s["N"], s["h"], s["w"]
-        rows = g.permute(0, 2, 3, 1)
-        if rows.dtype not in (torch.float32, L.TORCH_DTYPE[s["dt"]]):
-            rows = rows.float()
-        rows = rows.contiguous().view(N * h * w, AFF_FEAT_C)
-        if rows.data_ptr() % 16:
-            rows = rows.clone()
-        ds = aff_head_backward(s, rows)
-        return tuple(_nchw(d, N, h, w, dt_) if need else None for d, dt_, need in zip(ds, ctx.in_dtypes, ctx.needs_input_grad)) + (None, None)
+        ds = aff_head_backward(s, grad_to_rows(g, L.TORCH_DTYPE[s["dt"]]))
+        return tuple(rows_to_nchw(d, N, h, w, dt_) if need else None for d, dt_, need in zip(ds, ctx.in_dtypes, ctx.needs_input_grad)) + (None, None)
 
 
 def affinity_head(net, conv4, conv5, conv6):

@@ -6,6 +6,7 @@ network/resnet38_contrast.py:12-29) as *data*, so the host code, the weight pack
 the synthetic-weight generator all agree on the 233 state_dict keys.
 """
 from collections import OrderedDict
+from typing import NamedTuple
 
 # (name, kind, cin, mid, cout, stride, first_dilation, dilation, dropout)
 #   kind 'res' = ResBlock (two 3x3 convs), 'bot' = ResBlock_bot (1x1, 3x3, 1x1)
@@ -29,9 +30,9 @@ BLOCKS = [
     ("b7",   "bot", 2048, 1024, 4096, 1, 4, 4, 0.5),
 ]
 
-FROZEN_BLOCKS = ("b2", "b2_1", "b2_2")          # resnet38_contrast.py:29 (+ conv1a)
-N_FROZEN_BLOCKS = len(FROZEN_BLOCKS)            # they are the first blocks: the forward pass up to here depends on no trainable weight
-assert tuple(b[0] for b in BLOCKS[:N_FROZEN_BLOCKS]) == FROZEN_BLOCKS
+# resnet38_contrast.py:29 (+ conv1a): the reference's value for the contrast and affinity nets.  Each Net class states its own FROZEN_BLOCKS; the
+# engine derives everything else from it (prefix_of): they are leading blocks, so the forward pass up to there depends on no trainable weight
+FROZEN_BLOCKS = ("b2", "b2_1", "b2_2")
 HEAD_CONVS = OrderedDict([                       # resnet38_contrast.py:15-20
     ("fc8",     (21,  4096)),
     ("fc_proj", (128, 4096)),
@@ -83,6 +84,31 @@ def block_convs(b):
         out.append((f"{name}.conv_branch2b2", cout // 2, cout, 1, 1, 1))
         out.append((f"{name}.conv_branch1", cin, cout, 1, stride, 1))
     return out
+
+
+class Prefix(NamedTuple):
+    """The frozen prefix of a net as the engine reads it (prefix_of; one per Engine)"""
+    n: int                  # number of frozen blocks: BLOCKS[:n]
+    channels: int           # of the prefix's output: the last frozen block's, the stem's 64 for an empty prefix
+    trainable: tuple        # the rows of BLOCKS behind it
+    convs: tuple            # their block_convs rows, in flat-buffer order
+    first: str              # the first trainable block: its input comes from the prefix, so it gets weight gradients only
+    frozen_convs: tuple     # conv names of the frozen blocks (conv1a aside)
+    no_dgrad: frozenset     # the convs of the first trainable block that read its input: no data gradient, no transposed pack
+
+
+def prefix_of(net):
+    """Prefix of net.FROZEN_BLOCKS; refuses what the engine cannot serve: the frozen blocks are a leading run of BLOCKS, and the first trainable
+    block exists and is a ResBlock (Engine._trunk_backward handles a first block only in its ResBlock branch)."""
+    frozen, who = tuple(net.FROZEN_BLOCKS), f"{type(net).__module__}.{type(net).__qualname__}"
+    n = len(frozen)
+    if tuple(b[0] for b in BLOCKS[:n]) != frozen:
+        raise ValueError(f"{who}.FROZEN_BLOCKS = {frozen}: the engine serves a leading run of arch.BLOCKS (b2, b2_1, ...)")
+    if n == len(BLOCKS) or BLOCKS[n][1] != "res":
+        raise ValueError(f"{who}.FROZEN_BLOCKS = {frozen}: the first trainable block must exist and be a ResBlock")
+    return Prefix(n, BLOCKS[n - 1][4] if n else 64, tuple(BLOCKS[n:]), tuple(c for b in BLOCKS[n:] for c in block_convs(b)), BLOCKS[n][0],
+                  tuple(c[0] for b in BLOCKS[:n] for c in block_convs(b)),
+                  frozenset(c[0] for c in block_convs(BLOCKS[n]) if c[0].endswith(("branch2a", "branch1"))))
 
 
 def block_bns(b):

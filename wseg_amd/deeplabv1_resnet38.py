@@ -58,6 +58,8 @@ class Net(nn.Module):
     HEAD_KIND = "seg"
     HEAD_CONVS = arch.SEG_HEAD_CONVS
     FLAT_HEAD_ORDER = tuple(arch.SEG_HEAD_CONVS)
+    # the prefix the engine serves this net with today (inference does not depend on it); the reference trains from b2 on: the training change is this line
+    FROZEN_BLOCKS = arch.FROZEN_BLOCKS
 
     def __init__(self, precision=None):
         super().__init__()

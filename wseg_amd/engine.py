@@ -24,7 +24,6 @@ AFF_FEAT_C = 448       # AffinityNet feature rows [f8_3 64 | f8_4 128 | f8_5 256
 AFF_FEAT_SLICES = {"f8_3": (0, 64), "f8_4": (64, 192), "f8_5": (192, 448)}
 
 
-CONTRAST_FLAT_HEAD_ORDER = ("fc_proj", "fc8", "f8_3", "f8_4", "f9")
 DT_OF = {"bf16": L.BF16, "fp32": L.F32, "bf16x3": L.F32X3}   # bf16x3: f32 storage, conv / wgrad products as split-bf16 (3 bf16 MFMAs)
 
 
@@ -70,6 +69,52 @@ def block_launch_convs(b, din, dout):
 
 def head_conv(name, cin, cout, dims, k=1, dil=1):            # a head layer: a same-size conv on the stride-8 maps (1x1 but for DeepLab's conv_fov)
     return Conv(name, cin, cout, k, 1, dil, dims, dims)
+
+
+# ---- what the training-mode head modules (aff_head.py, seg_head.py) share
+def device_only(module, t, what):
+    if not t.is_cuda:
+        raise RuntimeError(f"wseg_amd.{module} runs only on an MI355X (HIP) device; there is no CPU fallback ({what} is on {t.device})")
+
+
+def head_backward_launchers(eng, P, launches, capture):
+    """(wgrad(name, x, dy), dgrad(name, dy, out, **operands)) of a head's backward over its `backward_launches` dict: the weight gradient of a
+    trainable conv into its slice of flat_g, the data gradient on the transposed pack P["wt"][name] with the epilogue operands; capture (a dict
+    or None) receives the plan of every data-gradient launch under "plans".  The keywords carry an explicit dtype: not _Pass.wgrad / dgrad."""
+    def wgrad(name, x, dy):
+        if eng.conv_param(name).requires_grad:
+            L.conv_wgrad(x, dy, eng.grad_slice(name), **launches["wgrad_" + name])
+
+    def dgrad(name, dy, out, **operands):
+        kw = dict(launches["dgrad_" + name], **operands)
+        if capture is not None:
+            capture.setdefault("plans", {})[name] = L.conv_plan(dy, P["wt"][name], out, None, **kw)
+        L.conv_igemm(dy, P["wt"][name], out, None, **kw)
+    return wgrad, dgrad
+
+
+def nchw_to_rows(x, tdt):
+    """NCHW -> contiguous pixel rows [N*h*w, C] in tdt (a channels_last tensor of that dtype is taken as it is)"""
+    N, C, h, w = x.shape
+    r = x.detach().permute(0, 2, 3, 1)
+    if r.dtype != tdt:
+        r = r.to(tdt)
+    return r.contiguous().view(N * h * w, C)
+
+
+def rows_to_nchw(rows, N, h, w, dtype):
+    """pixel rows -> the NCHW view in channels_last strides, in `dtype`"""
+    v = rows.view(N, h, w, rows.shape[1]).permute(0, 3, 1, 2)
+    return v if v.dtype == dtype else v.to(dtype)
+
+
+def grad_to_rows(g, tdt):
+    """an NCHW gradient -> contiguous, 16-byte aligned pixel rows [N*h*w, C] in float32 or tdt, what a head's backward takes"""
+    rows = g.permute(0, 2, 3, 1)
+    if rows.dtype not in (torch.float32, tdt):
+        rows = rows.float()
+    rows = rows.contiguous().view(-1, g.shape[1])
+    return rows.clone() if rows.data_ptr() % 16 else rows
 
 
 class _Pass:
@@ -159,6 +204,7 @@ class Engine:
 
     def __init__(self, net, parent=None):
         self._net_ref = weakref.ref(net)    # (no reference cycle; the Net owns the Engine)
+        self.prefix = arch.prefix_of(net)   # the frozen blocks, stated by the net's class, and what follows from them; refuses what cannot be served
         self.parent = parent                # replica: the engine of the module it was replicated from
         self.lock = threading.RLock()
         self.delegate = None                # set by ensure_flat on a replica that aliases its parent's flat buffer
@@ -212,16 +258,10 @@ class Engine:
         return mod
 
     def trainable_order(self):
-        """Flat-buffer order: backbone convs b3..b7, then the net's FLAT_HEAD_ORDER — for the contrast net fc_proj, fc8
-        (adjacent: the fused head GEMM's weight gradient is one [149,4096] block), f8_3, f8_4, f9."""
+        """Flat-buffer order: the convs of the trainable blocks (b3..b7 behind the reference's prefix), then the net's FLAT_HEAD_ORDER — for
+        the contrast net fc_proj, fc8 (adjacent: the fused head GEMM's weight gradient is one [149,4096] block), f8_3, f8_4, f9."""
         if self._order is None:
-            names = []
-            for b in arch.BLOCKS:
-                if b[0] in arch.FROZEN_BLOCKS:
-                    continue
-                names += [c[0] for c in arch.block_convs(b)]
-            names += list(getattr(self.net, "FLAT_HEAD_ORDER", CONTRAST_FLAT_HEAD_ORDER))
-            self._order = names
+            self._order = [c[0] for c in self.prefix.convs] + list(self.net.FLAT_HEAD_ORDER)
         return self._order
 
     def __deepcopy__(self, memo):
@@ -273,7 +313,7 @@ class Engine:
             p._wseg_flat = (self, off, p.numel())                # lets PolyOptimizer find the flat buffers
             self.offsets[n] = (off, p.numel())
             off += p.numel()
-        for n in ["conv1a"] + [c[0] for b in arch.BLOCKS if b[0] in arch.FROZEN_BLOCKS for c in arch.block_convs(b)]:
+        for n in ("conv1a",) + self.prefix.frozen_convs:
             p = self.conv_param(n)
             p.data = p.data.to(device).contiguous(memory_format=torch.channels_last)
         self.flat_w, self.flat_g = flat_w, flat_g
@@ -286,14 +326,13 @@ class Engine:
         """False when a parameter was modified through torch (load_state_dict, manual edits) since the mirror was written."""
         return self._mirror_pversions == tuple(self.conv_param(n_)._version for n_ in names)
 
-    def grad_buckets(self, after=("b7", "b5", "b4", "b3")):
+    def grad_buckets(self, after=None):
         """Contiguous slices of flat_g in the order backward completes them: {block name: (begin, end)} — the slice is
-        final once that block's weight gradients are enqueued (flat order = forward order; the heads sit behind b7)."""
-        firsts = {}
-        for b in arch.BLOCKS:
-            if b[0] in arch.FROZEN_BLOCKS:
-                continue
-            firsts[b[0]] = min(self.offsets[c[0]][0] for c in arch.block_convs(b))
+        final once that block's weight gradients are enqueued (flat order = forward order; the heads sit behind b7).
+        after: the trigger blocks, last first; default b7, b5, b4 as far as they lie behind the first trainable block, then that block."""
+        firsts = {b[0]: min(self.offsets[c[0]][0] for c in arch.block_convs(b)) for b in self.prefix.trainable}
+        if after is None:
+            after = tuple(nm for nm in ("b7", "b5", "b4") if nm in firsts and nm != self.prefix.first) + (self.prefix.first,)
         out, end = {}, self.flat_g.numel()
         for name in after:
             out[name] = (firsts[name], end)
@@ -357,11 +396,10 @@ class Engine:
         all buffers / BN parameters / frozen conv weights.  The frozen packs are rebuilt when it changes, and a lookahead prefix computed under
         another key is dropped (Trainer.step)."""
         net = self.net
-        frozen_names = [c[0] for b in arch.BLOCKS if b[0] in arch.FROZEN_BLOCKS for c in arch.block_convs(b)]
         # (the DeepLab head's folds — bn_fov, bn_fov2, cls_conv's bias — have a key of their own, seg_fold_key: a training step moves them)
         return (dt, str(device)) + tuple(b._version for n_, b in net.named_buffers() if not n_.startswith("bn_fov")) + \
             tuple(p._version for n_, p in net.named_parameters() if ".bn" in n_ or n_.startswith("bn7")) + \
-            tuple((self.conv_param(n_)._version, self.conv_param(n_).data_ptr()) for n_ in frozen_names) + \
+            tuple((self.conv_param(n_)._version, self.conv_param(n_).data_ptr()) for n_ in self.prefix.frozen_convs) + \
             (net.conv1a.weight._version, net.conv1a.weight.data_ptr())
 
     def seg_fold_key(self, device):
@@ -389,10 +427,10 @@ class Engine:
         fkey = self.frozen_key(device, dt)
         if self._frozen_packs is None or self._frozen_key != fkey:
             F_ = {"w": {}, "bn": {}}
-            for b in arch.BLOCKS:
+            for i, b in enumerate(arch.BLOCKS):
                 for (bname, c) in arch.block_bns(b):
                     F_["bn"][bname] = self._bn_fold(bname, device)
-                if b[0] in arch.FROZEN_BLOCKS:
+                if i < self.prefix.n:
                     for (cname, ci, co, k, s, d) in arch.block_convs(b):
                         wf = torch.empty(co, k * k, ci, device=device, dtype=tdt)
                         L.pack_weights(self.conv_param(cname).detach(), wf, None, co, k * k, ci, co, ci, L.F32 if dt == L.F32X3 else dt)
@@ -402,7 +440,7 @@ class Engine:
             self._frozen_packs, self._frozen_key = F_, fkey
             self._seg_fold_key = None
             self.packs = None
-        if getattr(net, "HEAD_KIND", "contrast") == "seg":
+        if net.HEAD_KIND == "seg":
             # DeepLab head (deeplabv1.py:42-49), eval mode: the two head BatchNorms folded like the backbone's; cls_conv's bias as the `shift` of its
             # launch, zero-padded to the pack's rows.  Keyed apart from the frozen packs (seg_fold_key), entered into their "bn" dict in place.
             skey = self.seg_fold_key(device)
@@ -419,7 +457,7 @@ class Engine:
         if self.packs is not None and key == self.pack_key:
             return self.packs
         P = {"w": dict(self._frozen_packs["w"]), "wt": {}, "bn": self._frozen_packs["bn"]}
-        no_dgrad = {"b3.conv_branch1", "b3.conv_branch2a"}
+        trunk_convs, no_dgrad = self.prefix.convs, self.prefix.no_dgrad
         # forward packs [OC][T][IC] have exactly the layout of the flat master buffer: in f32 mode they ARE views of
         # it, in bf16 mode they are views of ONE cast copy (a single launch instead of one per layer)
         if dt == L.BF16:
@@ -442,15 +480,12 @@ class Engine:
         if wt is not self.flat_wt:
             self.flat_wt = wt
             rows, tiles = [], 0
-            for b in arch.BLOCKS:
-                if b[0] in arch.FROZEN_BLOCKS:
+            for (cname, ci, co, k, s, d) in trunk_convs:
+                if cname in no_dgrad:
                     continue
-                for (cname, ci, co, k, s, d) in arch.block_convs(b):
-                    if cname in no_dgrad:
-                        continue
-                    off, n = self.offsets[cname]
-                    rows.append([tiles, off, off, co, k * k, ci])
-                    tiles += ((co + 31) // 32) * ((ci + 31) // 32) * k * k
+                off, n = self.offsets[cname]
+                rows.append([tiles, off, off, co, k * k, ci])
+                tiles += ((co + 31) // 32) * ((ci + 31) // 32) * k * k
             self._wt_table = torch.tensor(rows, dtype=torch.int64, device=device)
             self._wt_tiles = tiles
             rows64, t64 = [], 0                              # the bf16 -> bf16 variant works on 64x64 tiles
@@ -462,15 +497,13 @@ class Engine:
         self._wt_pending = (dt, mirror)
         if dt == L.F32X3:
             self.flat_wt3 = self._flat_like(self.flat_wt3, torch.float32, device)
-        for b in arch.BLOCKS:
-            if b[0] in arch.FROZEN_BLOCKS:
-                continue
-            for (cname, ci, co, k, s, d) in arch.block_convs(b):
-                T = k * k
-                off, n = self.offsets[cname]
-                P["w"][cname] = mirror[off:off + n].view(co, T, ci)
-                if cname not in no_dgrad:
-                    P["wt"][cname] = (self.flat_wt3 if dt == L.F32X3 else self.flat_wt)[off:off + n].view(ci, T, co)
+        for (cname, ci, co, k, s, d) in trunk_convs:
+            T = k * k
+            off, n = self.offsets[cname]
+            P["w"][cname] = mirror[off:off + n].view(co, T, ci)
+            if cname not in no_dgrad:
+                P["wt"][cname] = (self.flat_wt3 if dt == L.F32X3 else self.flat_wt)[off:off + n].view(ci, T, co)
+
         def late():
             # bf16 mode: a block's skip conv and its last conv as ONE two-source product (K-concatenation): rows [W_a[oc] | W_b[oc]] — the skip output is
             # then neither written nor re-read (444 MB each way for b7).  b6 / b7: [W_branch1 | W_branch2b2]; b5 (the residual-block form, 3x3 last conv +
@@ -481,14 +514,14 @@ class Engine:
                 for nm, buf in plan["fwd_bufs"].items():
                     P["w"][nm + ".skip_fused"] = buf
                 L.copy2d_batch(mirror, plan["fwd_flat"], plan["fwd_table"], plan["fwd_table"].shape[0], plan["fwd_chunks"])
-            if getattr(net, "HEAD_KIND", "contrast") == "aff":
+            if net.HEAD_KIND == "aff":
                 # AffinityNet head (resnet38_aff.py:13-17): four plain 1x1 packs, views of the mirror like the backbone's (every row is whole
                 # 32-element groups, so the split-bf16 mirror holds them too)
                 for nm, (co, ci) in net.HEAD_CONVS.items():
                     off, n = self.offsets[nm]
                     P["w"][nm] = mirror[off:off + n].view(co, 1, ci)
                 return
-            if getattr(net, "HEAD_KIND", "contrast") == "seg":
+            if net.HEAD_KIND == "seg":
                 # DeepLab head: conv_fov [512][9][4096] and conv_fov2 as views of the mirror; cls_conv's 21 rows copied into a pack zero-padded to
                 # 24 (every row is whole 32-element groups: the split-bf16 mirror's rows are copied as they are, and a zero row splits into zeros)
                 for nm, (co, ci, k) in net.HEAD_CONVS.items():
@@ -575,9 +608,9 @@ class Engine:
     def _fused_blocks(self):
         """[(name, kind, cin, mid, cout)] of the blocks whose skip conv and last conv run as one two-source launch (bf16 mode)"""
         out = []
-        for b in arch.BLOCKS:
+        for b in self.prefix.trainable:
             nm, kind, cin_, mid_, cout_, stride = b[0], b[1], b[2], b[3], b[4], b[5]
-            if nm in arch.FROZEN_BLOCKS or stride != 1 or cout_ % 256:
+            if stride != 1 or cout_ % 256:
                 continue
             if kind == "res" and not arch.block_same_shape(b) and cin_ % 256 == 0:
                 out.append((nm, kind, cin_, mid_, cout_))
@@ -666,7 +699,7 @@ class Engine:
         return outs[0]
 
     def _run_blocks(self, xs, state, first, last, save, S, final_t=None):
-        """Blocks arch.BLOCKS[first:last] (first == 0: conv1a first) over the batched views.  state: the dict an earlier call returned."""
+        """Blocks arch.BLOCKS[first:last] over the batched views.  state: the dict an earlier call returned; None: conv1a first."""
         V, dev, N = len(xs), xs[0].device, xs[0].shape[0]
         dt = DT_OF[self.net.precision]
         P = self.ensure_packs(dev, dt)
@@ -681,7 +714,7 @@ class Engine:
 
         sdims = {}
         conv4 = conv5 = None
-        if first == 0:
+        if state is None:
             dims = [(x.shape[2], x.shape[3]) for x in xs]
             sc, sh = P["bn"]["b2.bn_branch2a"]
             t = E(rows_of(dims), 64)
@@ -752,17 +785,17 @@ class Engine:
         """(rows, channels) of run_prefix's result for these views"""
         N = xs[0].shape[0]
         dims = [tuple(x.shape[2:]) for x in xs]
-        for b in arch.BLOCKS[:arch.N_FROZEN_BLOCKS]:
+        for b in arch.BLOCKS[:self.prefix.n]:
             dims = arch.block_out_dims(b, dims)
-        return sum(N * h * w for (h, w) in dims), arch.BLOCKS[arch.N_FROZEN_BLOCKS - 1][4]
+        return sum(N * h * w for (h, w) in dims), self.prefix.channels
 
     def run_prefix(self, xs, out=None):
-        """The part of the forward pass that depends on no trainable weight: conv1a and the blocks Net.train() freezes (b2, b2_1, b2_2;
+        """The part of the forward pass that depends on no trainable weight: conv1a and the blocks Net.train() freezes (the net's frozen blocks, self.prefix;
         resnet38_contrast.py:86-95 `not_training`), for one or two batched views.  Returns what run_forward continues from.  Because it depends only on the
         IMAGES, the fused step runs it for the NEXT batch on a side stream inside the loss phase of the current step (loss_hip.step `lookahead`).
         out: a [prefix_out_shape] tensor for the result — the fused step allocates it on the CALLER's stream, so that the one tensor that crosses from the
         prefix stream to the next step belongs to the caller's allocator pool (no record_stream bookkeeping: with it the reserved memory grew by 6 GB)."""
-        return self._run_blocks(xs, None, 0, arch.N_FROZEN_BLOCKS, False, None, final_t=out)
+        return self._run_blocks(xs, None, 0, self.prefix.n, False, None, final_t=out)
 
     def run_backbone(self, xs, save=False):
         """conv1a and every block, no head (the AffinityNet puts its own on top).  Returns (state, pass): state["t"] = relu(bn7(conv6)),
@@ -792,10 +825,10 @@ class Engine:
             masks["dropout7"] = None
         S = {"masks": masks, "dims": {}, "N": N, "V": V, "dt": dt, "xs": xs}
         if prefix is None:
-            prefix = self._run_blocks(xs, None, 0, arch.N_FROZEN_BLOCKS, keep_frozen, S if keep_frozen else None)
+            prefix = self._run_blocks(xs, None, 0, self.prefix.n, keep_frozen, S if keep_frozen else None)
         assert prefix["N"] == N and prefix["V"] == V and prefix["dt"] == dt and prefix["in_dims"] == [tuple(x.shape[2:]) for x in xs], \
             "the prefix was computed for another batch shape / precision"
-        st = self._run_blocks(xs, prefix, arch.N_FROZEN_BLOCKS, len(arch.BLOCKS), save, S)
+        st = self._run_blocks(xs, prefix, self.prefix.n, len(arch.BLOCKS), save, S)
         S["dims"].update(prefix["sdims"], **st["sdims"])
         self._join_late_packs(dev)
         ps = _Pass(self, N, dev, dt, P)
@@ -810,14 +843,14 @@ class Engine:
         gradients accumulate into flat_g, block_done fires as in run_backward; the PCM and contrast-head sections do not run."""
         tdt = L.TORCH_DTYPE[S["dt"]]
         taps = dict(taps or {})
-        blocks = {b[0]: b for b in arch.BLOCKS}
+        blocks = {b[0]: b for b in self.prefix.trainable[1:]}
         for nm, tap in list(taps.items()) + [("conv6", D)]:
             if nm == "conv6":
                 rows, c = S["M"], 4096
             else:
                 b = blocks.get(nm)
-                if b is None or nm in arch.FROZEN_BLOCKS or nm == "b3" or arch.block_same_shape(b):
-                    raise ValueError(f"run_trunk_backward: block {nm!r} takes no gradient tap (a trainable block with a skip conv, behind b3)")
+                if b is None or arch.block_same_shape(b):
+                    raise ValueError(f"run_trunk_backward: block {nm!r} takes no gradient tap (a trainable block with a skip conv, behind {self.prefix.first})")
                 rows, c = sum(S["N"] * h * w for (h, w) in S["dims"][nm][0]), b[2]
             if tuple(tap.shape) != (rows, c) or tap.dtype != tdt or tap.device != S["fea"].device:
                 raise ValueError(f"run_trunk_backward: the gradient at {nm} must be {tdt} rows [{rows}, {c}] on {S['fea'].device}, "
@@ -828,15 +861,20 @@ class Engine:
         self._trunk_backward(ps, S, dict(taps, conv6=D))
         ps.end_backward()
 
+    def _head_pass(self, t, N, ps):
+        """The pass a head launches on: `ps`, the one run_backbone returned, or (None) one on the current packs with the late packs joined"""
+        if ps is not None:
+            return ps
+        dev, dt = t.device, DT_OF[self.net.precision]
+        P = self.ensure_packs(dev, dt)
+        self._join_late_packs(dev)
+        return _Pass(self, N, dev, dt, P)
+
     def run_aff_head(self, conv4, conv5, t, dims, N, ps=None):
         """The AffinityNet head as a unit (network/resnet38_aff.py:39-42): the three 1x1 ELU convs of conv4 / conv5 / t = relu(bn7(conv6)) into the
         column slices [0,64) / [64,192) / [192,448) of `feat`, then f9 + ELU.  Inputs are pixel rows in the mode's dtype; returns (feat [M,448],
         f9 [M,448]).  ps: the pass run_backbone returned (inference); None: a pass on the current packs."""
-        if ps is None:
-            dev = t.device
-            P = self.ensure_packs(dev, DT_OF[self.net.precision])
-            self._join_late_packs(dev)
-            ps = _Pass(self, N, dev, DT_OF[self.net.precision], P)
+        ps = self._head_pass(t, N, ps)
         M = ps.rows_of(dims)
         C = AFF_FEAT_C
 
@@ -856,11 +894,7 @@ class Engine:
         conv_fov2 (1x1) + bn_fov2 + ReLU, cls_conv (1x1 + bias) on t = relu(bn7(conv6)), pixel rows in the mode's dtype.  Each launch writes
         only what the next one reads (`out2`, the affine form of the epilogue).  Returns the cls_conv pixel rows [M, 24] in the mode's dtype:
         21 logits and three zero columns.  ps: the pass run_backbone returned; None: a pass on the current packs."""
-        if ps is None:
-            dev = t.device
-            P = self.ensure_packs(dev, DT_OF[self.net.precision])
-            self._join_late_packs(dev)
-            ps = _Pass(self, N, dev, DT_OF[self.net.precision], P)
+        ps = self._head_pass(t, N, ps)
         M, bn = ps.rows_of(dims), ps.P["bn"]
         (c1, ci1, k1), (c2, ci2, _k2), (_c3, ci3, _k3) = arch.SEG_HEAD_CONVS.values()
         f1 = ps.E(M, c1)
@@ -877,11 +911,7 @@ class Engine:
         also updates the module's running statistics in place) and y = relu(z * scale + shift) (L.bn_relu_drop), the second with nn.Dropout's
         mask of `drop_key` (synth.dropout_keep); cls_conv as in inference, its bias read from the parameter into a persistent 24-element buffer.
         Returns (rows [M, 24], saved): saved holds z1, y1, z2, y2 and per BatchNorm stats [4, 512] f32 = mean, invstd, scale, shift."""
-        if ps is None:
-            dev = t.device
-            P = self.ensure_packs(dev, DT_OF[self.net.precision])
-            self._join_late_packs(dev)
-            ps = _Pass(self, N, dev, DT_OF[self.net.precision], P)
+        ps = self._head_pass(t, N, ps)
         net, dev, M = self.net, t.device, ps.rows_of(dims)
         if M * 512 >= 1 << 32:
             raise ValueError(f"run_seg_head_train: {M} rows of 512 channels pass the dropout mask's 32-bit counter")
@@ -912,42 +942,33 @@ class Engine:
 
     SEG_CLS_DGRAD_K = 64       # channels of the cls_conv data gradient's input: the conv launch walks K in 128-byte rows (64 bf16 / 32 f32)
 
-    def seg_head_wt(self, device):
-        """P["wt"] of the three DeepLab head convs, the data-gradient packs [IC][T][OC] in the mode's dtype (split-bf16: pre-split), made from the f32
-        masters on first use per set of packs, as aff_head_wt: inference never pays for them.  cls_conv's has SEG_CLS_DGRAD_K columns, 21 of them
-        its classes and the rest zero: its data gradient reads a gradient buffer zero-padded to that width.  Returns the current packs."""
+    def head_wt(self, device):
+        """P["wt"] of the net's HEAD_CONVS (the AffinityNet's four, DeepLab's three; the contrast head's are made with its forward packs), the
+        data-gradient packs [IC][T][OC] in the mode's dtype (split-bf16: pre-split), made from the f32 masters on first use per set of packs:
+        inference never pays for them.  A conv whose OC is no multiple of 8 (cls_conv) gets SEG_CLS_DGRAD_K columns, its classes and zeros
+        behind them: its data gradient reads a gradient buffer zero-padded to that width.  Returns the current packs."""
         dt = DT_OF[self.net.precision]
         with self.lock:
             P = self._ensure_packs(device, dt)
-            if "cls_conv" not in P["wt"]:
+            specs = self.head_wt_specs()
+            if specs[-1][0] not in P["wt"]:
                 pdt = L.F32 if dt == L.F32X3 else dt
-                for nm, (co, ci, k) in arch.SEG_HEAD_CONVS.items():
-                    off, n = self.offsets[nm]
-                    cop = co if co % 8 == 0 else self.SEG_CLS_DGRAD_K
-                    wt = torch.zeros(ci, k * k, cop, device=device, dtype=L.TORCH_DTYPE[dt])
-                    L.pack_weights(self.flat_w[off:off + n], None, wt, co, k * k, ci, cop, ci, pdt)
+                for nm, off, n, (ci, T, cop) in specs:
+                    co = n // (ci * T)
+                    wt = (torch.empty if cop == co else torch.zeros)(ci, T, cop, device=device, dtype=L.TORCH_DTYPE[dt])
+                    L.pack_weights(self.flat_w[off:off + n], None, wt, co, T, ci, cop, ci, pdt)
                     P["wt"][nm] = self._x3(wt) if dt == L.F32X3 else wt
         self._join_late_packs(device)
         return P
 
-    def aff_head_wt(self, device):
-        """P["wt"] of the four AffinityNet head convs, the data-gradient packs [IC][1][OC] in the mode's dtype (split-bf16: pre-split), made from the f32
-        masters on first use per set of packs: inference never pays for them.  Returns the current packs."""
-        dt = DT_OF[self.net.precision]
-        with self.lock:
-            P = self._ensure_packs(device, dt)
-            if "f9" not in P["wt"]:
-                pdt = L.F32 if dt == L.F32X3 else dt
-                for nm, off, n, (ci, _t, co) in self.aff_head_wt_specs():
-                    wt = torch.empty(ci, 1, co, device=device, dtype=L.TORCH_DTYPE[dt])
-                    L.pack_weights(self.flat_w[off:off + n], None, wt, co, 1, ci, co, ci, pdt)
-                    P["wt"][nm] = self._x3(wt) if dt == L.F32X3 else wt
-        self._join_late_packs(device)
-        return P
-
-    def aff_head_wt_specs(self):
-        """[(name, offset of its f32 master [OC][1][IC] in the flat buffers, numel, shape [IC][1][OC] of its transposed pack)] of the AffinityNet head"""
-        return [(nm, *self.offsets[nm], (ci, 1, co)) for nm, (co, ci) in self.net.HEAD_CONVS.items()]
+    def head_wt_specs(self):
+        """[(name, offset of its f32 master [OC][T][IC] in the flat buffers, numel, shape [IC][T][OC'] of its transposed pack)] of the net's
+        HEAD_CONVS, each (cout, cin) or (cout, cin, k); OC' = OC, or SEG_CLS_DGRAD_K where OC % 8 != 0"""
+        out = []
+        for nm, (co, ci, *k) in self.net.HEAD_CONVS.items():
+            T = k[0] ** 2 if k else 1
+            out.append((nm, *self.offsets[nm], (ci, T, co if co % 8 == 0 else self.SEG_CLS_DGRAD_K)))
+        return out
 
     def run_forward(self, xs, save, lowres=False, prefix=None):
         """xs: list of one or two image batches (same N).  Two views are BATCHED: every activation is one row
@@ -1112,17 +1133,14 @@ class Engine:
         who keeps no other reference (run_backward: 0.44 GB at the training shape) has it freed when b7 has consumed it, as every later Din is."""
         P, masks, D = ps.P, S["masks"], taps.pop("conv6")
         E, rows_of, wgrad, dgrad, block_done = ps.E, ps.rows_of, ps.wgrad, ps.dgrad, ps.block_done
-        for i in range(len(arch.BLOCKS) - 1, -1, -1):
-            b = arch.BLOCKS[i]
+        for b in reversed(self.prefix.trainable):
             name, kind, cin, mid, cout, stride, fd, d, p = b
-            if name in arch.FROZEN_BLOCKS:
-                break
             same = arch.block_same_shape(b)
             din, dout = S["dims"][name]
             Mi, Mo = rows_of(din), rows_of(dout)
             sv = S[name]
             sa, _ = P["bn"][name + ".bn_branch2a"]
-            first_trainable = name == "b3"               # its input comes from the frozen prefix
+            first_trainable = name == self.prefix.first  # its input comes from the frozen prefix
             cv = block_launch_convs(b, din, dout)
             c2a, c2b1, c1 = cv["branch2a"], cv["branch2b1"], cv.get("branch1")
             tap = taps.get(name)                         # a gradient w.r.t. this block's input t from outside the trunk: r_pre of the launch that writes Din (or tmp)

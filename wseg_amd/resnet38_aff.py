@@ -18,7 +18,7 @@ import torch.nn as nn
 from . import arch
 from . import engine
 from . import _lib as L
-from .resnet38_contrast import Net as _ContrastNet, Normalize, _Block
+from .resnet38_contrast import Net as _ContrastNet, Normalize, _Block, train_frozen
 
 FEAT_C = engine.AFF_FEAT_C                      # [f8_3 64 | f8_4 128 | f8_5 256]: the concat of resnet38_aff.py:47 is three column slices
 DEFAULT_RADIUS = 5
@@ -88,6 +88,7 @@ class Net(nn.Module):
     HEAD_KIND = "aff"
     HEAD_CONVS = arch.AFF_HEAD_CONVS
     FLAT_HEAD_ORDER = tuple(arch.AFF_HEAD_CONVS)
+    FROZEN_BLOCKS = arch.FROZEN_BLOCKS         # network/resnet38d.py:154 not_training, as the contrast net
 
     def __init__(self, precision=None):
         super().__init__()
@@ -104,7 +105,7 @@ class Net(nn.Module):
         nn.init.kaiming_normal_(self.f8_4.weight)
         nn.init.kaiming_normal_(self.f8_5.weight)
         nn.init.xavier_uniform_(self.f9.weight, gain=4)
-        self.not_training = [self.conv1a, self.b2, self.b2_1, self.b2_2]
+        self.not_training = [self.conv1a] + [getattr(self, b) for b in self.FROZEN_BLOCKS]
         self.from_scratch_layers = [self.f8_3, self.f8_4, self.f8_5, self.f9]
         self.predefined_featuresize = PREDEFINED_FEATURESIZE
         self.radius = DEFAULT_RADIUS
@@ -204,21 +205,4 @@ class Net(nn.Module):
                     (groups[3] if m in self.from_scratch_layers else groups[1]).append(m.bias)
         return groups
 
-    def train(self, mode=True):
-        """network/resnet38d.py:192-214: frozen prefix + every BatchNorm in eval and frozen (forward still refuses training mode: see affinities_train)."""
-        super().train(mode)
-        for layer in self.not_training:
-            if isinstance(layer, nn.Conv2d):
-                layer.weight.requires_grad = False
-            elif isinstance(layer, nn.Module):
-                for c in layer.children():
-                    if getattr(c, "weight", None) is not None:
-                        c.weight.requires_grad = False
-                    if getattr(c, "bias", None) is not None:
-                        c.bias.requires_grad = False
-        for layer in self.modules():
-            if isinstance(layer, nn.BatchNorm2d):
-                layer.eval()
-                layer.bias.requires_grad = False
-                layer.weight.requires_grad = False
-        return self
+    train = train_frozen                       # (forward still refuses training mode: see affinities_train)

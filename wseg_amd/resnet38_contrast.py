@@ -58,10 +58,32 @@ class Normalize:
         return proc_img
 
 
+def train_frozen(net, mode=True):
+    """network/resnet38d.py:192-214, the train() of the contrast and affinity nets: `not_training` (conv1a and the net's FROZEN_BLOCKS) frozen,
+    every BatchNorm in eval and frozen."""
+    nn.Module.train(net, mode)
+    for layer in net.not_training:
+        if isinstance(layer, nn.Conv2d):
+            layer.weight.requires_grad = False
+        elif isinstance(layer, nn.Module):
+            for c in layer.children():
+                if getattr(c, "weight", None) is not None:
+                    c.weight.requires_grad = False
+                if getattr(c, "bias", None) is not None:
+                    c.bias.requires_grad = False
+    for layer in net.modules():
+        if isinstance(layer, nn.BatchNorm2d):
+            layer.eval()
+            layer.bias.requires_grad = False
+            layer.weight.requires_grad = False
+    return net
+
+
 class Net(nn.Module):
     HEAD_KIND = "contrast"                     # the engine's head table (arch.HEAD_CONVS) and flat-buffer order of the head weights
     HEAD_CONVS = arch.HEAD_CONVS
-    FLAT_HEAD_ORDER = engine.CONTRAST_FLAT_HEAD_ORDER
+    FLAT_HEAD_ORDER = ("fc_proj", "fc8", "f8_3", "f8_4", "f9")     # fc_proj, fc8 adjacent: the fused head GEMM's weight gradient is one [149,4096] block
+    FROZEN_BLOCKS = arch.FROZEN_BLOCKS         # the leading blocks train() freezes with conv1a (resnet38_contrast.py:29): the engine's prefix
 
     def __init__(self, precision=None):
         super().__init__()
@@ -82,7 +104,7 @@ class Net(nn.Module):
         nn.init.xavier_uniform_(self.f9.weight, gain=4)
         nn.init.xavier_uniform_(self.fc_proj.weight)
         self.from_scratch_layers = [self.f8_3, self.f8_4, self.f9, self.fc8, self.fc_proj]
-        self.not_training = [self.conv1a, self.b2, self.b2_1, self.b2_2]
+        self.not_training = [self.conv1a] + [getattr(self, b) for b in self.FROZEN_BLOCKS]
         self.normalize = Normalize()
         self.precision = precision or os.environ.get("WSEG_PRECISION", "bf16")
         assert self.precision in ("bf16", "fp32", "bf16x3")      # bf16x3: f32 storage, conv / wgrad products as split-bf16 (wseg_hip.h WSEG_F32X3)
@@ -124,21 +146,4 @@ class Net(nn.Module):
                     (groups[3] if m in self.from_scratch_layers else groups[1]).append(m.bias)
         return groups
 
-    def train(self, mode=True):
-        """network/resnet38d.py:192-214: frozen prefix + every BatchNorm in eval and frozen."""
-        super().train(mode)
-        for layer in self.not_training:
-            if isinstance(layer, nn.Conv2d):
-                layer.weight.requires_grad = False
-            elif isinstance(layer, nn.Module):
-                for c in layer.children():
-                    if getattr(c, "weight", None) is not None:
-                        c.weight.requires_grad = False
-                    if getattr(c, "bias", None) is not None:
-                        c.bias.requires_grad = False
-        for layer in self.modules():
-            if isinstance(layer, nn.BatchNorm2d):
-                layer.eval()
-                layer.bias.requires_grad = False
-                layer.weight.requires_grad = False
-        return self
+    train = train_frozen

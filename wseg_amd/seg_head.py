@@ -22,18 +22,16 @@ tensors.  d_t takes the optional bn7-ReLU operands (scale / mask / drop: epilogu
 outside the conv weight gradients (some of whose kernels add with float atomics) is bit-identical from run to run.  Nothing synchronises with
 the host.  The rest of the stage — the backbone's backward from d_t, the data path, the trainer — does not exist yet.
 """
+import functools
+
 import torch
 
 from . import arch
 from . import _lib as L
-from .engine import DT_OF, Engine, head_conv
+from .engine import DT_OF, Engine, device_only, grad_to_rows, head_backward_launchers, head_conv, nchw_to_rows, rows_to_nchw
 
 CONVS = tuple(arch.SEG_HEAD_CONVS)                                  # conv_fov, conv_fov2, cls_conv
-
-
-def _device_only(t, what):
-    if not t.is_cuda:
-        raise RuntimeError(f"wseg_amd.seg_head runs only on an MI355X (HIP) device; there is no CPU fallback ({what} is on {t.device})")
+_device_only = functools.partial(device_only, "seg_head")
 
 
 def _conv(name, dims, cout=None):
@@ -98,20 +96,11 @@ def seg_head_backward(ctx, d_rows, scale=None, mask=None, drop=None, capture=Non
         raise ValueError(f"seg_head_backward: d_rows must be [{M}, >= {arch.SEG_CLS_ROWS}] rows in float32 or {tdt}, "
                          f"got {tuple(d_rows.shape)} {d_rows.dtype}")
     dev, net = d_rows.device, eng.net
-    P = eng.seg_head_wt(dev)
+    P = eng.head_wt(dev)
     eng.attach_grads()
     launches = backward_launches(N, h, w, dt, epi1=any(o is not None for o in (scale, mask, drop)))
+    wgrad, dgrad = head_backward_launchers(eng, P, launches, capture)
     ws = torch.empty(L.bn_stats_workspace_bytes(M, 512), device=dev, dtype=torch.uint8)
-
-    def wgrad(name, x, dy):
-        if eng.conv_param(name).requires_grad:
-            L.conv_wgrad(x, dy, eng.grad_slice(name), **launches["wgrad_" + name])
-
-    def dgrad(name, dy, out, **operands):
-        kw = dict(launches["dgrad_" + name], **operands)
-        if capture is not None:
-            capture.setdefault("plans", {})[name] = L.conv_plan(dy, P["wt"][name], out, None, **kw)
-        L.conv_igemm(dy, P["wt"][name], out, None, **kw)
 
     def bn_backward(i, g, s):
         bn = eng.bn_module(arch.SEG_HEAD_BNS[CONVS[i - 1]][0])
@@ -156,13 +145,10 @@ class SegHead(torch.autograd.Function):
     @staticmethod
     def forward(ctx, conv6, anchor, net, drop_key):
         N, _, h, w = conv6.shape
-        tdt = L.TORCH_DTYPE[DT_OF[net.precision]]
-        r = conv6.detach().permute(0, 2, 3, 1)
-        r = (r if r.dtype == tdt else r.to(tdt)).contiguous().view(N * h * w, 4096)
-        rows, ctx.saved = seg_head_forward(net, r, N, h, w, drop_key)
+        rows, ctx.saved = seg_head_forward(net, nchw_to_rows(conv6, L.TORCH_DTYPE[DT_OF[net.precision]]), N, h, w, drop_key)
         ctx.in_dtype = conv6.dtype
         ctx.set_materialize_grads(False)
-        return rows.view(N, h, w, arch.SEG_CLS_ROWS).permute(0, 3, 1, 2)
+        return rows_to_nchw(rows, N, h, w, rows.dtype)
 
     @staticmethod
     def backward(ctx, g):
@@ -170,17 +156,8 @@ class SegHead(torch.autograd.Function):
             return None, None, None, None
         s = ctx.saved
         N, h, w = s["N"], s["h"], s["w"]
-        rows = g.permute(0, 2, 3, 1)
-        if rows.dtype not in (torch.float32, L.TORCH_DTYPE[s["dt"]]):
-            rows = rows.float()
-        rows = rows.contiguous().view(N * h * w, arch.SEG_CLS_ROWS)
-        if rows.data_ptr() % 16:
-            rows = rows.clone()
-        d_t = seg_head_backward(s, rows)
-        if not ctx.needs_input_grad[0]:
-            return None, None, None, None
-        v = d_t.view(N, h, w, 4096).permute(0, 3, 1, 2)
-        return (v if v.dtype == ctx.in_dtype else v.to(ctx.in_dtype)), None, None, None
+        d_t = seg_head_backward(s, grad_to_rows(g, L.TORCH_DTYPE[s["dt"]]))
+        return (rows_to_nchw(d_t, N, h, w, ctx.in_dtype) if ctx.needs_input_grad[0] else None), None, None, None
 
 
 def seg_head(net, conv6, drop_key):
