@@ -22,16 +22,16 @@ import torch
 import torch.nn.functional as F
 
 from .f64_bars import SAFETY, U32, _gen, _interp_bar
+# the float64 references and bars of the PCM kernels, shared with the stage tests of the head passes (KF = 192 feature channels; BAND_CAP,
+# the largest share of (i, j) pairs whose gate may be undecided at sbar; BF16_RND per value the bf16 kernels round, SPLIT_T the
+# split-precision gate product: see the module docstring)
+from .head_f64 import BAND_CAP, BF16_RND, KF, SPLIT_T, _pcm_bwd_reference, _pcm_fwd64, _pcm_fwd_bars, _ulp_bf16
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-KF = 192                    # PCM feature channels
 GUARD = 64                  # sentinel elements behind an output buffer
 SENT = 7.0
-BAND_CAP = 1e-3             # largest share of (i, j) pairs whose gate may be undecided at sbar
-BF16_RND = 2.0 ** -9        # per value the bf16 kernels round (see the module docstring)
-SPLIT_T = 3.0 * 2.0 ** -17  # the split-precision gate product
 
 
 def _L():
@@ -49,11 +49,6 @@ def _guarded(numel, fill, dtype=torch.float32):
 
 def _guard_ok(whole):
     return bool((whole[-GUARD:].cpu().float() == SENT).all())
-
-
-def _ulp_bf16(x):
-    """one bf16 ulp of a float64 value (a result stored in bf16)"""
-    return torch.exp2(torch.floor(torch.log2(x.abs().clamp_min(2.0 ** -126))) - 7)
 
 
 def _i16(t):
@@ -148,28 +143,6 @@ def _pcm_inputs(N, hw, seed, exact=False):
     return Fh, _gate_like(N * hw, g), torch.randn(N, 21, hw, generator=g)
 
 
-def _pcm_fwd64(Fh, G):
-    """one image, float64: Fh [hw,192], G [hw,32] -> rv [21,hw], den [hw], S [hw,hw] (S[i,j])"""
-    S = Fh @ Fh.T
-    out = torch.relu(S).T @ G                                 # out[j][c] = sum_i relu(S_ij) G_ic (relu: autograd closes the gate at S == 0)
-    den = out[:, 21]
-    return (out[:, :21] / (den + 1e-5)[:, None]).T, den, S
-
-
-def _pcm_fwd_bars(Fh, G, hw, relu_rel=0.0):
-    """raw error of one image's S, and the bars of rv [21,hw] and den [hw].
-    S: a chain of 192 on sum_k |Fh_ik Fh_jk|.  out[j][c] = sum_i relu(S_ij) G_ic (all terms >= 0): relu is 1-Lipschitz, so every
-    term moves by <= (eS_ij + relu_rel relu(S_ij)) G_ic, and the i-loop is a chain of hw on out itself.  rv = out / (den + 1e-5):
-    the add and the f32 constant 1 u of D each, the division 1 u of rv."""
-    rv, den, S = _pcm_fwd64(Fh, G)
-    eS = KF * U32 * (Fh.abs() @ Fh.abs().T)
-    out = S.clamp_min(0).T @ G
-    e_out = (eS + relu_rel * S.clamp_min(0)).T @ G + hw * U32 * out
-    D = den + 1e-5
-    bar_rv = SAFETY * ((e_out[:, :21] + rv.T.abs() * (e_out[:, 21] + 2 * U32 * D)[:, None]) / D[:, None] + U32 * rv.T.abs()).T
-    return rv, den, S, eS, bar_rv, SAFETY * e_out[:, 21]
-
-
 def _assert_balanced(S_list, hw):
     if hw == 1:                                               # the single pair is the diagonal, S = |Fh|^2 = 1
         return
@@ -223,50 +196,6 @@ def test_pcm_forward_small_denominator(hw):
     rv_k, den_k = _run_pcm_forward(L.pcm_forward, Fh.to(DEV), G.to(DEV), N, hw)
     _check_pcm_forward(rv_k, den_k, Fh.double(), G.double(), N, hw)
     assert float(den_k.max()) < 1e-4
-
-
-def _pcm_bwd_reference(Fh, G, g, rv_in, den_in, hw, base, t_chain, t_rel=0.0, w_rel=0.0, with_band=True):
-    """One image in float64.  Fh [hw,192], G [hw,32], g = d_cam_rv [21,hw], rv_in / den_in the f32 values handed to the kernel,
-    base [hw,192] the dFh the kernel accumulates onto.  Returns the autograd gradient of sum(g * rv) with respect to Fh (G
-    constant), its elementwise bar, DN by its formula with its bar, and the number of pairs inside the gate band.
-
-    DN[j][c] = g_jc * (1 / (den_j + 1e-5)): the add, the constant, the division and the product = 4 u;  DN[j][21] = -(sum_c g rv) * inv:
-    a chain of 21 and 1 u per product on sum|g rv|, then the same 4 u.
-    t_ij = sum_c P_ic Q_jc over the 32 gate channels: a chain of t_chain, + t_rel of sum|P||Q| (the split product), + DN's own error
-    and the roundings of the rv / den inputs (u each) through |G|.  W = gate * t (+ w_rel |t| where W is rounded to bf16).
-    dFh[j][k] += sum_i W_ij Fh_ik, twice (t_ij and t_ji): each a chain of hw on sum_i |W_ij Fh_ik|, each `+=` 1 u of its result.
-    Gate flips: a row i with |S_ij| <= sbar_ij (sbar = SAFETY * 192 u sum_k |Fh_ik Fh_jk|) may be gated either way by the kernel:
-    |t_ij| |Fh_ik| from each launch, in float64."""
-    x = Fh.clone().requires_grad_(True)
-    rv, _, _ = _pcm_fwd64(x, G)
-    (rv * g).sum().backward()
-    ref = x.grad
-    S = Fh @ Fh.T
-    gate = S > 0
-    gT, rvT = g.T, rv_in.T                                    # [hw,21]
-    Dn = (den_in + 1e-5)[:, None]
-    grv = (gT * rvT).abs().sum(1, keepdim=True)
-    DN = torch.zeros(hw, 32, dtype=torch.float64)
-    DN[:, :21] = gT / Dn
-    DN[:, 21:22] = -(gT * rvT).sum(1, keepdim=True) / Dn
-    eDN = 4 * U32 * DN.abs()
-    eDN[:, 21:22] += 22 * U32 * grv / Dn
-    e_in = 2 * U32 * DN.abs()                                 # rv_in, den_in = f32(float64 reference): 1 u each
-    e_in[:, 21:22] += 2 * U32 * grv / Dn
-    t = G @ DN.T                                              # t[i,j] = sum_c G_ic DN_jc
-    ta = G.abs() @ DN.abs().T
-    e_t = (t_chain * U32 + t_rel) * ta + G.abs() @ (eDN + e_in).T + w_rel * t.abs()
-    Fa = Fh.abs()
-    if with_band:
-        band = S.abs() <= SAFETY * KF * U32 * (Fa @ Fa.T)
-    else:                                                     # S exact in f32: no undecided gate
-        band = torch.zeros_like(gate)
-    sym = lambda M: (M + M.T).T @ Fa                          # [j,k] = sum_i (M_ij + M_ji) |Fh_ik|
-    live = (gate | band).double()
-    mag = sym(gate.double() * t.abs())
-    arith = hw * U32 * mag + sym(live * e_t) + 2 * U32 * (base.abs() + mag)
-    flip = sym(band.double() * t.abs())
-    return ref, SAFETY * arith + flip, DN, SAFETY * eDN, int(band.sum())
 
 
 def _pcm_bwd_case(hw, seed, exact, with_base):
