@@ -19,6 +19,9 @@ import torch
 import torch.nn.functional as F
 
 from .f64_bars import SAFETY, U32, _bits, _coord_bar, _gen, _interp_bar     # (shared with test_gpu_pcm_head_kernels.py)
+# the float64 references and bar helpers live in tests/loss_f64.py, where the stage judge of the loss phase (test_gpu_loss_stages.py) uses them too
+from .loss_f64 import (NCE_CI, NCE_MAX_EXCLUDED, S_BAR, _exact_grid, _label_full, _max_norm_inj, _nce_reference, _nce_sum_bar, _proto_bar, _protos64,
+                       _resize64, _resize_bwd64, _select_ref, _stats_chain, _up64, sampling_rule)
 
 pytestmark = pytest.mark.gpu
 
@@ -30,24 +33,9 @@ def _L():
     return L
 
 
-def _up64(low, S):
-    """bilinear align_corners=True upsample of [planes, h, w] -> [planes, S, S] in float64."""
-    return F.interpolate(low.double()[None], size=(S, S), mode="bilinear", align_corners=True)[0]
-
-
 # ------------------------------------------------------------------------------------------------ planar resize (head.hip)
 RESIZE_CASES = [(56, 56, 448, 448), (21, 21, 500, 500), (16, 16, 128, 128), (448, 448, 56, 56), (16, 16, 16, 16),
                 (13, 11, 97, 40), (7, 5, 1, 1), (1, 1, 9, 9)]
-
-
-def _resize64(x, oh, ow, align):
-    return F.interpolate(x.double()[None], size=(oh, ow), mode="bilinear", align_corners=align)[0]
-
-
-def _resize_bwd64(g, ih, iw, align):
-    x = torch.zeros(g.shape[0], ih, iw, dtype=torch.float64, requires_grad=True)
-    (_resize64(x, g.shape[1], g.shape[2], align) * g.double()).sum().backward()
-    return x.grad
 
 
 @pytest.mark.parametrize("align", [True, False])
@@ -125,16 +113,6 @@ def _value_set(kind, rows, n, g):
     raise ValueError(kind)
 
 
-def _select_ref(v64, k, largest, use_abs, relu):
-    f = v64.abs() if use_abs else v64
-    thr = torch.sort(f, dim=1, descending=largest).values[:, k - 1]
-    beyond = f > thr[:, None] if largest else f < thr[:, None]
-    term = f.clamp_min(0) if relu else f
-    zero = torch.zeros((), dtype=torch.float64)
-    return (thr, torch.where(beyond, term, zero).sum(1), beyond.sum(1).double(), (f == thr[:, None]).sum(1).double(),
-            torch.where(beyond, term.abs(), zero).sum(1))
-
-
 def _same_nonfinite(a, b):
     return (math.isnan(a) and math.isnan(b)) or a == b
 
@@ -194,19 +172,10 @@ def _special_planes(low):
     return low
 
 
-def _stats_chain(S, chunks):
-    # up_stats_partial: S*S / (256 chunks) serial adds per thread, an 8-level LDS tree, then `chunks` same-address atomics
-    return math.ceil(S * S / (256 * chunks)) + 8 + chunks
-
-
 # (h, w, S, planes): 448 / 128 / 160 crops, non-square + odd S, the S > 1024 plain-column loop, planes > 4096 (chunks = 1),
 # and a dyadic grid (scales 1/8 and 1/16) on which U is exact: ties and first-index rules are asserted exactly there
 UP_STATS_CASES = [(56, 56, 448, 42), (16, 16, 128, 42), (20, 20, 160, 21), (13, 11, 97, 21), (130, 130, 1040, 2),
                   (5, 5, 40, 4200), (17, 9, 129, 21)]
-
-
-def _exact_grid(h, w, S):
-    return (h - 1) * 16 % (S - 1) == 0 and (w - 1) * 16 % (S - 1) == 0
 
 
 @pytest.mark.parametrize("h,w,S,planes", UP_STATS_CASES)
@@ -355,14 +324,6 @@ def test_up_rvmin_values_and_min_pool_loss(h, w, S):
 
 
 # ------------------------------------------------------------------------------------------------ max-norm + resize
-def _max_norm_inj(U, imx, imn, e=1e-5):
-    """max_norm of [planes, S*S] with max / min taken at the given positions (the kernel's decisions)."""
-    R = U.clamp_min(0)
-    rows = torch.arange(U.shape[0])
-    mx, mn = R[rows, imx][:, None], R[rows, imn][:, None]
-    return (R - mn - e).clamp_min(0) / (mx - mn + e)
-
-
 @pytest.mark.parametrize("h,w,S", [(56, 56, 448), (20, 20, 160), (16, 16, 128), (13, 11, 97)])
 def test_up_norm_resize_forward(h, w, S):
     L = _L()
@@ -405,10 +366,6 @@ def test_resize_adjoint_ones(h, S):
 
 
 # ------------------------------------------------------------------------------------------------ up_maps_backward
-def _label_full(label20):
-    return torch.cat([torch.ones(label20.shape[0], 1), label20], 1).double()
-
-
 MAPS_BWD_CASES = ([(56, 56, 448, t) for t in ("cam", "rv")] +
                   [(h, w, S, t) for h, w, S in [(16, 16, 128), (13, 11, 97), (17, 9, 129)] for t in ("norm", "bias", "sel", "cam", "rv")])
 
@@ -697,23 +654,6 @@ def _candidates(ncam, feat, K, tie):
     return cv, cf, cc
 
 
-def _protos64(vals, feats):
-    """float64 weighted mean + F.normalize over a given candidate set: vals [21, K], feats [21, K, 128]."""
-    v, f = vals.double(), feats.double()
-    return F.normalize((v[:, :, None] * f).sum(1) / v.sum(1, keepdim=True), dim=-1)
-
-
-def _proto_bar(vals, feats, K):
-    # acc: K products + K adds (2K roundings of sum|v f|), wsum: K adds of sum|v|, the division 1; then the norm (a 2-wave
-    # block sum: 7 levels, sqrt, max, division: 10 roundings) relative to the prototype
-    v, f = vals.double(), feats.double()
-    ws = v.sum(1, keepdim=True)
-    pr = (v[:, :, None] * f).sum(1) / ws
-    dpr = (2 * K * U32 * (v[:, :, None] * f).abs().sum(1) + pr.abs() * K * U32 * v.abs().sum(1, keepdim=True)) / ws.abs() + U32 * pr.abs()
-    nrm = pr.norm(dim=1, keepdim=True)
-    return SAFETY * (dpr / nrm + dpr.norm(dim=1, keepdim=True) / nrm * (pr.abs() / nrm) + 10 * U32 * pr.abs() / nrm)
-
-
 @pytest.mark.parametrize("n", [1, 16, 128])
 def test_proto_candidates_and_merge(n):
     """n = 128: P = 32768, the wrapper's LDS limit (P * 4 = 128 KiB of values in one workgroup); one more image is refused."""
@@ -788,82 +728,6 @@ def test_proto_non_finite_values(n):
 
 
 # ------------------------------------------------------------------------------------------------ pixel-to-prototype contrast (nce.hip)
-# delta S, the error of one f32 similarity against normalize(F) . p in float64 (|S| <= 1): the row norm is a 32-term lane chain plus
-# two shuffles (34), the contraction a chain of at most 128 MFMA partial sums with sum|terms| <= |F| |p| = |F| (Cauchy-Schwarz; the
-# prototypes are unit vectors), scaled by 1 / |F|.  S_ERR is the raw figure, S_BAR the bar (the safety factor applied once).
-S_ERR = (128 + 34) * U32
-S_BAR = SAFETY * S_ERR                       # 1.9e-5
-ITAU = 10.0                                  # 1 / tau, tau = 0.1
-NCE_CI = 0.05                                # coef_intra; coef_cross = 0.1 / (2 P) (the step's values at world 1)
-NCE_MAX_EXCLUDED = 0.02                      # share of pixels per view whose rank band 3..12 may be undecided at S_BAR
-
-
-def _nce_reference(V, cc, ci, with_grad):
-    """float64 restatement of contrast_train.py:245-334 for both views (tau = 0.1): per view the per-pixel cross-prototype,
-    cross-pseudo-label and intra-view terms, the rank band, and (with_grad) dF through the F.normalize backward with the
-    elementwise error bar of the kernel's chain.  V[i]: F, p, y, w (f32 / int CPU tensors); w is used as given."""
-    out = []
-    for v, o in ((V[0], V[1]), (V[1], V[0])):
-        P = v["F"].shape[0]
-        F64 = v["F"].double()
-        nr = F64.norm(dim=1, keepdim=True)
-        fn = F64 / nr.clamp_min(1e-12)
-        Po, Pt = v["p"].double(), o["p"].double()
-        So, St = fn @ Po.T, fn @ Pt.T
-        yo, yt = v["y"].long()[:, None], o["y"].long()[:, None]
-        # semi-hard negatives: similarity ranks 3..12, descending, the lower class first on a tie (:293-294)
-        srt, order = torch.sort(So, dim=1, descending=True, stable=True)
-        neg = torch.zeros(P, 21, dtype=torch.float64).scatter_(1, order[:, 3:13], 1.0)
-        gap = torch.minimum(srt[:, 2] - srt[:, 3], srt[:, 12] - srt[:, 13])
-        dead = nr[:, 0] == 0                                  # S == 0 exactly on both sides: the stated tie rule decides, exactly
-        r = dict(So=So, yo=yo, undecided=(gap < 2 * S_BAR) & ~dead, dead=dead)
-        Eo, Et = torch.exp(ITAU * So), torch.exp(ITAU * St)
-        oh_yo = torch.zeros(P, 21, dtype=torch.float64).scatter_(1, yo, 1.0)
-        oh_yt = torch.zeros(P, 21, dtype=torch.float64).scatter_(1, yt, 1.0)
-        m = neg + oh_yo                                       # the positive, and the band (the positive again if it lies inside)
-        a2 = (m * Eo).sum(1, keepdim=True)
-        sig_o, sig_t, q = Eo / Eo.sum(1, keepdim=True), Et / Et.sum(1, keepdim=True), m * Eo / a2
-        r["L"] = (-torch.log(sig_t.gather(1, yo))[:, 0], -torch.log(sig_o.gather(1, yt))[:, 0], -torch.log(Eo.gather(1, yo) / a2)[:, 0])
-        if with_grad:
-            w = v["w"].double()[:, None]
-            kc, ki = cc * ITAU, ci * ITAU * w
-            dSo = kc * (sig_o - oh_yt) + ki * (q - oh_yo)
-            dSt = kc * (sig_t - oh_yo)
-            dfn = dSo @ Po + dSt @ Pt
-            dot = (dfn * fn).sum(1, keepdim=True)
-            inv = torch.where(dead[:, None], torch.zeros((), dtype=torch.float64), 1.0 / nr.clamp_min(1e-300))
-            r["dF"] = (dfn - fn * dot) * inv
-            # ---- the bar of dF, term by term (raw errors; SAFETY once at the end)
-            # e = expf(10 S): the product rounds (10 u on the exponent), expf 2 u -> 12 u relative; a softmax entry s = e / sum: 12 u
-            # + (12 + 21) u of the 21-term sum + 1 u of the division = 46 u relative; through delta S it moves by
-            # sum_j |ds/dS_j| S_ERR = 10 s * 2 (1 - s) S_ERR <= 20 s S_ERR.  The same holds for q (entries sum to 1, <= 13 terms).
-            # dS = kc (s - [c == y]) + ki (q - [c == y]): each difference 1 rounding, kc 1 and ki 2 roundings and their products 1
-            # each (<= 4 u of the term), the final add 1 u of dS.
-            rel = 20 * S_ERR + 46 * U32
-            e_dSo = rel * (kc * sig_o + ki * q) + 4 * U32 * (kc * (sig_o - oh_yt).abs() + ki * (q - oh_yo).abs()) + U32 * dSo.abs()
-            e_dSt = rel * kc * sig_t + 5 * U32 * dSt.abs()
-            # d fn = dS . P: a chain of 44 MFMA terms on sum |dS| |P|
-            e_dfn = e_dSo @ Po.abs() + e_dSt @ Pt.abs() + 44 * U32 * (dSo.abs() @ Po.abs() + dSt.abs() @ Pt.abs())
-            # fn = F * (1 / |F|): the norm 17 u (half of the 34-chain of its square) + sqrt, reciprocal, product: 20 u, the product
-            # 1 u more; dot = sum_128 dfn fn: 32 products per lane + 2 shuffles (34) and 1 u per product
-            e_dot = (e_dfn * fn.abs()).sum(1, keepdim=True) + (21 + 35) * U32 * (dfn * fn).abs().sum(1, keepdim=True)
-            # dF = (dfn - fn dot) * inv: fn dot carries fn's 21 u and 1 u, the difference 1 u, inv 20 u and the product 1 u
-            bar = inv * (e_dfn + fn.abs() * e_dot + 22 * U32 * (fn * dot).abs()) + 22 * U32 * r["dF"].abs()
-            r["dF_bar"] = SAFETY * bar
-        out.append(r)
-    return out
-
-
-def _nce_sum_bar(L, weight, P):
-    """|sum_f32 - sum_64| of one loss sum = sum_p weight_p L_p.  Per pixel L = -log(e_y / sum_c e_c) moves by 20 S_ERR through delta S
-    (sum_c |dL/dS_c| = 10 * 2 (1 - s_y) <= 20), by (12 + 12 + 21 + 1) u through exp / sum / division into the log, and by 2 u |L| (logf, the
-    coefficient).  The accumulation: `trips` serial adds per lane, a 6-level wave tree, 4 waves, one same-address atomic per workgroup."""
-    groups = 2 * ((P + 63) // 64)
-    blocks = min(2048, (groups + 3) // 4)
-    chain = math.ceil(groups / (4 * blocks)) + 6 + 4 + blocks
-    return SAFETY * float((weight * (20 * S_ERR + 46 * U32 + 2 * U32 * L.abs())).sum() + chain * U32 * (weight * L.abs()).sum())
-
-
 @pytest.fixture(scope="module", params=[77, 1000, 4096, 300007])
 def nce_case(request):
     """Inputs of both views (the generators of the retired fused-vs-unfused test) and their float64 reference, built once per P.
@@ -987,18 +851,9 @@ def test_intra_weights_against_the_sampling_rule():
     L.intra_weights(y.to(DEV), S.to(DEV), rk.to(DEV), None, w, P)
     yn, rkn = y.numpy(), rk.numpy()
     sim = S.numpy()[np.arange(P), yn]
-    ref = np.zeros(P)
     present = np.unique(yn)
     assert 7 not in present and int((yn == 19).sum()) == 1
-    for c in present:
-        idx = np.nonzero(yn == c)[0]                          # ascending pixel index: a stable sort keeps it among equal keys
-        n = len(idx)
-        if n < 2:
-            continue
-        half, kk = n // 2, int(n * 0.6)
-        unit = 1.0 / (2 * half * len(present))
-        ref[idx[np.argsort(rkn[idx], kind="stable")[:half]]] += unit
-        ref[idx[np.argsort(sim[idx], kind="stable")[kk - half:kk]]] += unit
+    ref = sampling_rule(yn, sim, rkn=rkn)
     got = w.cpu().double().numpy()
     assert ref.sum() > 0 and (got[ref == 0] == 0).all()
     np.testing.assert_allclose(got, ref, rtol=1e-6, atol=0)
